@@ -125,6 +125,24 @@ def make_inputs(seed, B, n, nt, dt):
     return q, dq, t
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(arrays, out_dir):
+    """--dump-outputs: every array (float32 / float64, rows first) -> out_dir/<name>.npy.  Above DUMP_MAX_BYTES in all,
+    every array keeps the same seeded, sorted sample of rows, so that two builds' files still compare row for row."""
+    B = next(iter(arrays.values())).shape[0]
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64) and v.shape[0] == B, (k, v.dtype, v.shape)
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.RandomState(0).choice(B, B * DUMP_MAX_BYTES // total, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), v)
+
+
 class Runner:
     """device-resident inputs + one launch per step()"""
 
@@ -344,8 +362,25 @@ class Runner:
             self.engine.osc_generate(self.arm_id, self.n, self.params, self.q, self.dq, self.t, u=self.u,
                                      dtype=self.dt, device=self.device, stream=self.stream)
 
-    def timed(self, steps, warmup, barrier=None):
-        """-> (wall seconds of the timed region, mean kernel ms per launch from HIP events)"""
+    def outputs(self):
+        """name -> device array: what a caller of this workload's path receives (the rollout: the advanced state)"""
+        if self.kind == "ik":
+            return {"position_path": self.ik_out[0], "velocity_path": self.ik_out[1]}
+        if self.kind == "rollout":
+            return {"q": self.q, "dq": self.dq}
+        if self.kind == "dyn":
+            return dict(self.dyn_out)
+        out = {"u": self.u}
+        if self.kind == "osc_full":
+            out.update(self.dyn_out)
+        if hasattr(self, "ts"):
+            out["training_signal"] = self.ts
+        return out
+
+    def timed(self, steps, warmup, barrier=None, keep_outputs=False):
+        """-> (wall seconds of the timed region, mean kernel ms per launch from HIP events).  keep_outputs: host copies
+        of outputs() as the last timed step left them, in self.last_outputs (taken before the HIP-event replay below,
+        which would advance the rollout's state once more)"""
         a = self.a
         if self.plan is not None and 8 <= steps < self.graph_steps:
             self.graph_steps = steps  # a short run is one graph of exactly K nodes
@@ -390,6 +425,8 @@ class Runner:
         wall = time.perf_counter() - t0
         if barrier:
             barrier()
+        if keep_outputs:
+            self.last_outputs = {k: v.numpy(self.stream) for k, v in self.outputs().items()}
         # the HIP-event time per launch (the `roofline*` blocks) comes from one more, untimed replay of the same K
         # steps: recording the two events inside the wall-clocked region costs ~5 us of host time, which at K = 20
         # config-sized steps is 5 % of the run
@@ -863,6 +900,8 @@ def single_process(args):
 
     runs = [Runner(args.workload, B, d, a.Stream(d)) for d in devices]
     wall, t_enq = timed(runs, args.steps, args.warmup)
+    if args.dump_outputs:  # the recorded plans compute the same outputs on every tick: the last one is what they hold
+        dump_outputs({k: v.numpy(runs[0].stream) for k, v in runs[0].outputs().items()}, args.dump_outputs)
     out = {
         "metric": "OSC control steps/sec (batched UR5 6-DOF)" if args.workload == "cfg2" else f"control steps/sec ({args.workload})",
         "value": round(N * B * args.steps / wall, 1), "unit": "control steps/s", "n_gpus": N, "n_devices_seen": seen,
@@ -923,6 +962,9 @@ def main():
                     help="every HBM-sized leg then runs back to back for this long; `roofline.frac` = mean of the last "
                          "second (0: quote the short run of --roofline-steps launches, as the PMC passes do)")
     ap.add_argument("--dump-shard-u", default="", help="directory: every rank writes the sha256 of its cfg4 shard's u")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path computed in its last timed step (rank 0, device 0 of "
+                         "--single-process) as DIR/<name>.npy; above 64 MB in all, a fixed seeded sample of rows")
     ap.add_argument("--no-extras", action="store_true", help="skip the osc6 and shard_sweep legs of the default line")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline-leg", action="store_true")
@@ -942,6 +984,8 @@ def main():
     ap.add_argument("--also", default="", help="comma-separated extra workloads: one HBM-sized roofline leg each "
                                                "(same process, so one rocprofv3 session sees every kernel)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from abr_control_amd.sharding import dist_env
 
@@ -985,7 +1029,10 @@ def main():
     run = Runner(args.workload, B, device, stream)
 
     barrier = group.barrier if group else None
-    wall, ms = run.timed(args.steps, args.warmup, barrier)
+    wall, ms = run.timed(args.steps, args.warmup, barrier, keep_outputs=bool(args.dump_outputs) and rank == 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(run.last_outputs, args.dump_outputs)
+        del run.last_outputs
     # the same step when the fixed cost of a (graph) launch is amortised: 2000 steps, HIP events (not `value`)
     ms_long = None
     if rank == 0 and args.steps < 1000 and kind not in ("rollout", "ik"):

@@ -34,21 +34,23 @@ import re
 import shutil
 import subprocess
 import sys
+import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
-SCRATCH = "/tmp/abrk_ref_scratch"
 OUT = os.path.join(REPO, "tests", "golden")
 ARMS = ["twojoint", "threejoint", "ur5", "jaco2", "onejoint"]
 
 
 def make_scratch():
+    """-> a private, writable scratch copy of the reference with the numpy-2 shim applied"""
     if not os.path.isdir(REF):
         sys.exit("gen_golden.py needs /root/reference (build container only)")
-    if os.path.isdir(SCRATCH):
-        shutil.rmtree(SCRATCH)
-    shutil.copytree(REF, SCRATCH)
-    path = os.path.join(SCRATCH, "abr_control", "utils", "transformations.py")
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from time_reference import writable_copy
+
+    scratch = writable_copy(REF, os.path.join(tempfile.mkdtemp(prefix="abrk_ref_scratch_"), "ref"))
+    path = os.path.join(scratch, "abr_control", "utils", "transformations.py")
     src = open(path).read()
     src, n = re.subn(
         r"numpy\.array\(([^()]*?), dtype=numpy\.float64, copy=False\)",
@@ -56,7 +58,8 @@ def make_scratch():
         src,
     )
     open(path, "w").write(src)
-    print(f"scratch copy at {SCRATCH}; numpy-2 shim applied at {n} sites")
+    print(f"scratch copy at {scratch}; numpy-2 shim applied at {n} sites")
+    return scratch
 
 
 def main():
@@ -65,18 +68,21 @@ def main():
     if args[:1] == ["--out"]:  # tests/test_reference_provenance.py regenerates into a scratch directory and diffs
         OUT, args = os.path.abspath(args[1]), args[2:]
     which = args or ARMS + ["known"]
-    make_scratch()
+    scratch = make_scratch()
     env = dict(os.environ)
     env["PYTHONDONTWRITEBYTECODE"] = "1"
-    env["PYTHONPATH"] = SCRATCH
+    env["PYTHONPATH"] = scratch
     os.makedirs(OUT, exist_ok=True)
-    for w in which:
-        print(f"==== {w}", flush=True)
-        subprocess.run(
-            [sys.executable, os.path.join(REPO, "oracle", "_gen_golden_worker.py"), w, OUT],
-            env=env,
-            check=True,
-        )
+    try:
+        for w in which:
+            print(f"==== {w}", flush=True)
+            subprocess.run(
+                [sys.executable, os.path.join(REPO, "oracle", "_gen_golden_worker.py"), w, OUT],
+                env=env,
+                check=True,
+            )
+    finally:
+        shutil.rmtree(os.path.dirname(scratch), ignore_errors=True)
 
 
 if __name__ == "__main__":

@@ -28,7 +28,6 @@ import time
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
-SCRATCH = "/tmp/abrk_ref_scratch_timing"
 
 WORKLOADS = {
     # name: (arm, controller factory source, n target columns)
@@ -79,6 +78,17 @@ def numpy2_shim(pkg_root):
                      r"numpy.asarray(\1, dtype=numpy.float64)", src)
     open(path, "w").write(src)
     return n
+
+
+def writable_copy(src, dst, **kw):
+    """shutil.copytree(src, dst, **kw), then every copied file and directory made writable by its owner: the reference
+    checkout is read-only, copytree keeps those modes, and a scratch copy is edited (numpy2_shim), written into by the
+    reference's own code and removed again - as any user, not only as root"""
+    shutil.copytree(src, dst, **kw)
+    for dp, _, fns in os.walk(dst):
+        for p in [dp] + [os.path.join(dp, f) for f in fns]:
+            os.chmod(p, os.stat(p).st_mode | 0o200)
+    return dst
 
 
 def ref_env(pkg_root, home=None):
@@ -158,17 +168,15 @@ def main():
         if res is None:
             sys.exit("time_reference.py: neither /root/reference nor a staged oracle/_ref archive (or sympy/Cython missing)")
     else:
-        if os.path.isdir(SCRATCH):
-            shutil.rmtree(SCRATCH)
-        shutil.copytree(REF, SCRATCH)
-        numpy2_shim(SCRATCH)
+        scratch = writable_copy(REF, os.path.join(tempfile.mkdtemp(prefix="abrk_ref_timing_"), "ref"))
+        numpy2_shim(scratch)
         cpu, _ = host_description()
         res = {"measured_on": f"build container ({cpu}, {cores} cores) - NOT the GPU box's host",
                "what": "abr_control's own Cython path: ctrlr.generate(q[b], dq[b], target[b]) per row (no batch API), "
                        "generated functions loaded from its cache (base_config.py:173-191)",
                "script": "oracle/time_reference.py", "cores": cores,
-               "workloads": measure(list(WORKLOADS), ref_env(SCRATCH), cores)}
-        shutil.rmtree(SCRATCH, ignore_errors=True)
+               "workloads": measure(list(WORKLOADS), ref_env(scratch), cores)}
+        shutil.rmtree(os.path.dirname(scratch), ignore_errors=True)
     for name, v in res["workloads"].items():
         print(name, v, flush=True)
     os.makedirs(os.path.dirname(out), exist_ok=True)

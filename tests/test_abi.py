@@ -32,7 +32,7 @@ def test_every_declared_symbol_is_exported(L):
     assert L.abrk_version() == 100
 
 
-def test_struct_layouts_match_header():
+def test_struct_layouts_match_header(tmp_path):
     """ctypes mirrors vs the C structs (sizes computed by compiling a probe with the real header)"""
     src = r'''
 #include <stdio.h>
@@ -42,7 +42,7 @@ int main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", s
   sizeof(abrk_limits_params), sizeof(abrk_obstacles_params), offsetof(abrk_obstacles_params, obstacles),
   sizeof(abrk_scratch_info), offsetof(abrk_scratch_info, device_free_bytes), sizeof(abrk_shard_cut),
   offsetof(abrk_shard_cut, rows), offsetof(abrk_shard_cut, streams));return 0;}'''
-    exe = "/tmp/abrk_layout_probe"
+    exe = str(tmp_path / "abrk_layout_probe")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(REPO, "include"), "-o", exe], input=src.encode(),
                    check=True)
     sizes = [int(v) for v in subprocess.run([exe], capture_output=True, check=True).stdout.split()]

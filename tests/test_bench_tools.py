@@ -38,6 +38,26 @@ def test_algorithmic_bytes_follow_the_survey():
     assert bench.algorithmic_bytes(6, 8, "dyn", ("Tx", "J", "M", "g")) == 696
 
 
+def test_dump_outputs_keeps_a_seeded_row_sample_under_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: small outputs are written whole; above the cap every array keeps the SAME seeded rows, in order,
+    and the files stay under the cap"""
+    import bench
+
+    rng = np.random.RandomState(5)
+    u, M = rng.standard_normal((1000, 6)), rng.standard_normal((1000, 6, 6)).astype(np.float32)
+    bench.dump_outputs({"u": u, "M": M}, str(tmp_path / "whole"))
+    assert np.array_equal(np.load(tmp_path / "whole" / "u.npy"), u)
+    assert np.load(tmp_path / "whole" / "M.npy").dtype == np.float32
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 40_000)
+    for d in ("a", "b"):
+        bench.dump_outputs({"u": u, "M": M}, str(tmp_path / d))
+    us, Ms = np.load(tmp_path / "a" / "u.npy"), np.load(tmp_path / "a" / "M.npy")
+    assert 0 < len(us) == len(Ms) < 1000 and us.nbytes + Ms.nbytes <= 40_000
+    rows = [int(np.flatnonzero((u == r).all(axis=1))[0]) for r in us]
+    assert rows == sorted(rows) and np.array_equal(Ms, M[rows])
+    assert np.array_equal(np.load(tmp_path / "b" / "u.npy"), us)  # same sample from run to run
+
+
 def test_summarize_profiles_keys_grid_stride_kernels_by_rows(tmp_path):
     src, dst = tmp_path / "run", tmp_path / "out"
     (src / "pmc_FETCH_SIZE").mkdir(parents=True)

@@ -1082,6 +1082,34 @@ def test_gpu_bench_workloads_match_the_oracle(workload):
         r.plan.close()
 
 
+def test_gpu_bench_dumps_what_the_timed_path_computed(tmp_path):
+    """`bench.py --gpus 1 --steps K --dump-outputs DIR`: the line reports the K timed steps and their ms_per_step, and
+    DIR/u.npy is bit-equal to one step of the same recorded plan on the same seeded inputs"""
+    import json
+    import subprocess
+    import sys
+
+    import abr_control_amd as a
+    from tests.conftest import REPO
+
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "3",
+           "--dump-outputs", str(tmp_path), "--no-roofline-leg", "--no-strong-leg", "--no-cpu-baseline"]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=REPO)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 30 and d["ms_per_step"] > 0
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 4096) < 1e-3 * 4096  # value = rows x steps / (steps x ms_per_step)
+    assert sorted(os.listdir(tmp_path)) == ["u.npy"]
+    bench = _bench_module()
+    st = a.Stream(0)
+    r = bench.Runner("cfg2", 4096, 0, st)
+    r.step()
+    st.sync()
+    u = np.load(tmp_path / "u.npy")
+    assert u.dtype == np.float64 and np.array_equal(u, r.u.numpy())
+    r.plan.close()
+
+
 @pytest.mark.parametrize("launcher", ["self", "external"])
 def test_gpu_bench_two_ranks_share_one_device(tmp_path, launcher):
     """the N > 1 launch contract on a one-GPU box: plain `python bench.py --gpus 2` (the command launches its own ranks;

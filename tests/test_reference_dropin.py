@@ -19,7 +19,6 @@ import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
-SCRATCH = "/tmp/abrk_ref_scratch_dropin"
 
 pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "abr_control")),
                                 reason="needs the reference checkout (build container only)")
@@ -63,14 +62,14 @@ json.dump({"u": u.tolist(), "kinds": kinds, "exc": exc, "udtype": str(u.dtype)},
 
 
 @pytest.fixture(scope="module")
-def ref_env():
-    if os.path.isdir(SCRATCH):
-        shutil.rmtree(SCRATCH)
-    shutil.copytree(REF, SCRATCH, ignore=shutil.ignore_patterns("__pycache__"))
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1", PYTHONPATH=SCRATCH, HOME="/tmp/abrk_ref_scratch_dropin_home")
+def ref_env(tmp_path_factory):
+    from oracle.time_reference import writable_copy
+
+    root = tmp_path_factory.mktemp("ref_dropin")
+    scratch = writable_copy(REF, str(root / "ref"), ignore=shutil.ignore_patterns("__pycache__"))
+    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1", PYTHONPATH=scratch, HOME=str(root / "home"))
     yield env
-    shutil.rmtree(SCRATCH, ignore_errors=True)
-    shutil.rmtree("/tmp/abrk_ref_scratch_dropin_home", ignore_errors=True)
+    shutil.rmtree(root, ignore_errors=True)
 
 
 @pytest.mark.parametrize("arm,case,rows", [("ur5", "cfg2", 96), ("ur5", "cfg4", 64), ("jaco2", "cfg3", 64),

@@ -18,23 +18,25 @@ import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
-SCRATCH = "/tmp/abrk_ref_scratch_prov"
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "abr_control")),
-                                reason="needs the reference checkout (build container only)")
+needs_reference = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "abr_control")),
+                                     reason="needs the reference checkout (build container only)")
 
 
 @pytest.fixture(scope="module")
-def ref_env():
+def ref_env(tmp_path_factory):
     # never import the reference from where it lies: imports write __pycache__ / pyximport artefacts (hazard 1)
-    if os.path.isdir(SCRATCH):
-        shutil.rmtree(SCRATCH)
-    shutil.copytree(REF, SCRATCH)
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1", PYTHONPATH=SCRATCH)
+    from oracle.time_reference import writable_copy
+
+    root = tmp_path_factory.mktemp("ref_prov")
+    scratch = writable_copy(REF, str(root / "ref"))
+    # its own HOME: the reference writes its function cache and pyximport builds under ~
+    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1", PYTHONPATH=scratch, HOME=str(root / "home"))
     yield env
-    shutil.rmtree(SCRATCH, ignore_errors=True)
+    shutil.rmtree(root, ignore_errors=True)
 
 
+@needs_reference
 @pytest.mark.parametrize("arm", ["onejoint", "twojoint", "threejoint", "ur5", "jaco2"])
 def test_extractor_reproduces_committed_table(arm, ref_env, tmp_path):
     out = tmp_path / f"{arm}.json"
@@ -60,6 +62,7 @@ def test_extractor_keeps_non_literal_constants():
     assert len(w) == 1
 
 
+@needs_reference
 def test_gen_golden_reproduces_committed_fixture(tmp_path):
     arms = [a for a in os.environ.get("ABRK_PROVENANCE_ARMS", "onejoint").split(",") if a]
     out = tmp_path / "golden"
