@@ -45,6 +45,13 @@ class ArmDesc(C.Structure):
     ]
 
 
+class ArmInertia(C.Structure):  # abrk_arm_inertia: full link / joint inertias of a general-inertia arm
+    _fields_ = [
+        ("mlink", (C.c_double * 36) * (MAX_JOINTS + 1)),
+        ("mjoint", (C.c_double * 36) * MAX_JOINTS),
+    ]
+
+
 class DynOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("Tx", "J", "M", "g", "C", "dJ", "R", "T", "Tinv", "quat")]
 
@@ -236,6 +243,69 @@ def desc_from_table(tab):
     return d
 
 
+def _inertia_list(tab, key, count, what):
+    """the 6x6 matrices of `tab[key]` as float arrays (exactly `count` of them), checked for symmetry"""
+    mats = [np.asarray(m, dtype=np.float64) for m in tab[key]]
+    if len(mats) != count or any(m.shape != (6, 6) for m in mats):
+        raise ValueError(f"{key}: expected {count} matrices of 6x6 ({what})")
+    for i, m in enumerate(mats):
+        if not np.all(np.isfinite(m)):
+            raise ValueError(f"{key}[{i}] has non-finite entries")
+        if not np.array_equal(m, m.T):
+            raise ValueError(f"{key}[{i}] is not symmetric: inertia matrices must be (M == M.T, exactly)")
+    return mats
+
+
+def normalize_table(tab):
+    """Validate the optional full inertias of an arm table and return the table the kernels run:
+    `mlink` (n_joints + 1 matrices, 6x6: the reference's _M_LINKS) and `mjoint` (n_joints matrices: _M_JOINTS).
+    An arm is general-inertia only if some `mlink` has an off-diagonal entry or some `mjoint` is non-zero; otherwise the
+    plain table (`mdiag` only) is returned - same kernels, same results, same plugin cache key as without the keys.
+    Raises ValueError for an asymmetric matrix or a diagonal `mlink` that differs from `mdiag`."""
+    if "mlink" not in tab and "mjoint" not in tab:
+        return tab
+    n = int(tab["n_joints"])
+    md = [np.asarray(tab["mdiag"][l] if l < len(tab["mdiag"]) else [0.0] * 6, dtype=np.float64) for l in range(n + 1)]
+    ml = _inertia_list(tab, "mlink", n + 1, "one per link, link0 included") if "mlink" in tab else None
+    mj = _inertia_list(tab, "mjoint", n, "one per joint") if "mjoint" in tab else None
+    off = False
+    if ml is not None:
+        for l, m in enumerate(ml):
+            if np.any(m != np.diag(np.diag(m))):
+                off = True
+            elif not np.array_equal(np.diag(m), md[l]):
+                raise ValueError(f"mlink[{l}] is diagonal but differs from mdiag[{l}]")
+    gi = off or (mj is not None and any(np.any(m != 0) for m in mj))
+    out = {k: v for k, v in tab.items() if k not in ("mlink", "mjoint")}
+    if gi:
+        out["mlink"] = [m.tolist() for m in ml] if ml is not None else [np.diag(d).tolist() for d in md]
+        out["mjoint"] = [m.tolist() for m in mj] if mj is not None else [[[0.0] * 6] * 6] * n
+    return out
+
+
+def is_general_inertia(tab):
+    """True for a table with full link inertias or joint inertias that the plain form cannot express"""
+    return "mlink" in normalize_table(tab)
+
+
+def inertia_from_table(tab):
+    """abrk_arm_inertia of a table: its full inertias, or the plain form (diag(mdiag), zero joint inertias)"""
+    t = normalize_table(tab)
+    n = int(t["n_joints"])
+    out = ArmInertia()
+    for l in range(n + 1):
+        m = np.asarray(t["mlink"][l], dtype=np.float64) if "mlink" in t else np.diag(
+            np.asarray(t["mdiag"][l] if l < len(t["mdiag"]) else [0.0] * 6, dtype=np.float64))
+        for e in range(36):
+            out.mlink[l][e] = m.reshape(36)[e]
+    if "mjoint" in t:
+        for j in range(n):
+            m = np.asarray(t["mjoint"][j], dtype=np.float64).reshape(36)
+            for e in range(36):
+                out.mjoint[j][e] = m[e]
+    return out
+
+
 def render_tab_struct(t, struct_name, name=None):
     """C++ source of the constexpr arm table `struct <struct_name>` the StaticArm kernels are instantiated on
     (abrk_arms_builtin.h for the built-in arms, the plugin source of a compiled user arm).  Literals are `repr`
@@ -247,6 +317,7 @@ def render_tab_struct(t, struct_name, name=None):
         return "{" + ", ".join(lit(v) for row in m for v in row) + "}"
 
     ident = [[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0]]
+    t = normalize_table(t)
     n = int(t["n_joints"])
     md = [list(r) for r in t["mdiag"]] + [[0.0] * 6] * (n + 1 - len(t["mdiag"]))
     out = [
@@ -260,6 +331,14 @@ def render_tab_struct(t, struct_name, name=None):
         f"  static constexpr double E[12] = {mat(t['E'] if t['has_ee'] else ident)};",
         f"  static constexpr double MD[{n + 1}][6] = {{" + ",\n      ".join(
             "{" + ", ".join(lit(v) for v in row) + "}" for row in md[: n + 1]) + "};",
+    ]
+    if "mlink" in t:  # general inertias (abrk_device.h StaticArm::kGI): full link inertias ML, joint inertias MJ
+        out += [
+            "  static constexpr bool kGI = true;",
+            f"  static constexpr double ML[{n + 1}][36] = {{" + ",\n      ".join(mat(m) for m in t["mlink"]) + "};",
+            f"  static constexpr double MJ[{n}][36] = {{" + ",\n      ".join(mat(m) for m in t["mjoint"]) + "};",
+        ]
+    out += [
         f'  static constexpr const char* kName = "{name if name is not None else t.get("name", "robot")}";',
         "};",
     ]

@@ -39,6 +39,9 @@ def lib():
         L.abrk_arm_create_compiled.argtypes = [C.POINTER(_abi.ArmDesc), C.c_char_p]
         L.abrk_plugin_abi.restype = C.c_char_p
         L.abrk_arm_get_desc.argtypes = [C.c_int, C.POINTER(_abi.ArmDesc)]
+        L.abrk_arm_create_compiled_inertia.argtypes = [C.POINTER(_abi.ArmDesc), C.POINTER(_abi.ArmInertia),
+                                                       C.c_char_p]
+        L.abrk_arm_get_inertia.argtypes = [C.c_int, C.POINTER(_abi.ArmInertia)]
         L.abrk_arm_destroy.argtypes = [C.c_int]
         L.abrk_dynamics_batch.argtypes = [
             C.c_int, C.c_int, _i64, _vp, _vp, C.c_int, C.POINTER(C.c_double), C.c_uint32,

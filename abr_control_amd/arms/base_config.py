@@ -42,13 +42,22 @@ class BatchedConfig:
         kernels specialised for this table (abr_control_amd/specialize.py - the counterpart of the reference's cached
         generated functions, base_config.py:173-191).  None (default): use the cached plugin when there is one, else
         the runtime-table kernels.  True: build it now if it is not cached (one hipcc run, 1-3 min).  False: never.
+        A general-inertia table (full link inertias `mlink` / joint inertias `mjoint`, _abi.normalize_table) runs on
+        compiled kernels only: None behaves as True, and False is refused.
     """
 
     def __init__(self, table, builtin=None, use_cython=True, dtype=np.float64, device=0,
                  reference_dtypes=True, compiled=None, **kwargs):
         if kwargs:
             raise TypeError(f"unexpected keyword arguments {sorted(kwargs)}")  # as base_config.py:78 would
+        table = _abi.normalize_table(table)  # ValueError for asymmetric / inconsistent inertias
         self.table = table
+        self.general_inertia = "mlink" in table
+        if self.general_inertia:
+            if compiled is False:
+                raise ValueError("a general-inertia arm table (mlink / mjoint) runs on compiled kernels only; "
+                                 "the runtime-table kernels (compiled=False) take diagonal link inertias")
+            compiled = True
         self.N_JOINTS = int(table["n_joints"])
         self.N_LINKS = int(table["n_links_dyn"])
         self.ROBOT_NAME = table.get("name", "robot")
@@ -60,8 +69,12 @@ class BatchedConfig:
         n = self.N_JOINTS
         # reference attributes consumers read (interfaces/pygame.py:72-73, arm_sim.py:27-30)
         md = table["mdiag"]
-        self._M_LINKS = [np.diag(np.asarray(md[l], dtype=float)) for l in range(len(md))]
-        self._M_JOINTS = [np.zeros((6, 6)) for _ in range(n)]
+        if self.general_inertia:
+            self._M_LINKS = [np.array(m, dtype=float) for m in table["mlink"]]
+            self._M_JOINTS = [np.array(m, dtype=float) for m in table["mjoint"]]
+        else:
+            self._M_LINKS = [np.diag(np.asarray(md[l], dtype=float)) for l in range(len(md))]
+            self._M_JOINTS = [np.zeros((6, 6)) for _ in range(n)]
         rows = [np.asarray(table["A0"])[:, 3]]
         for i in range(n):
             rows.append(np.asarray(table["AJ"][i])[:, 3])
@@ -89,7 +102,12 @@ class BatchedConfig:
                     from .. import specialize
 
                     path = specialize.compile_arm(self.table) if self._compiled else specialize.find_compiled(self.table)
-                if path:
+                if path and self.general_inertia:
+                    inertia = _abi.inertia_from_table(self.table)
+                    self._arm_id = check(lib().abrk_arm_create_compiled_inertia(C.byref(desc), C.byref(inertia),
+                                                                                path.encode()))
+                    self._plugin_path = path
+                elif path:
                     self._arm_id = check(lib().abrk_arm_create_compiled(C.byref(desc), path.encode()))
                     self._plugin_path = path
                 else:

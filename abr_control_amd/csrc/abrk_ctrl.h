@@ -1820,7 +1820,8 @@ ABRK_INL void osc_row(const A& arm, const OscP<T>& P, const T (&q)[A::N], const 
   // in `scr` - LDS on the GPU, so the 12 N registers they would take stay free and the kernel keeps two waves per
   // SIMD -; one backward sweep (rne_backward) then projects the sums onto the joint axes.  (Until round 2 the
   // recursion ran as a pass of its own with a second forward kinematics: +128 instructions per row.)
-  constexpr bool TWO_PASS = USE_C && !MAT && A::kOrtho;
+  // (general-inertia arms: their extra Coriolis terms ride on the per-link form, CMODE_VEC - abrk_device.h gi_frame)
+  constexpr bool TWO_PASS = USE_C && !MAT && A::kOrtho && !A::kGI;
   // the frame rotation of an orthogonal chain is a product of exact rotations: one power step in quat_from_R
   constexpr int kQSteps = A::kOrthoFrames ? 1 : 3;
   Joints<A, T> jt;

@@ -303,6 +303,13 @@ constexpr bool aff_is_orthogonal(const double* X) {
   return det > 0.0;
 }
 
+// does the table struct carry full link / joint inertias (abr_control_amd/_abi.py render_tab_struct, general-inertia
+// arms)?  Tables without the member - every built-in arm - are plain.
+template <class Tab, class = void>
+struct tab_gi : std::false_type {};
+template <class Tab>
+struct tab_gi<Tab, std::void_t<decltype(Tab::kGI)>> : std::integral_constant<bool, Tab::kGI> {};
+
 // Built-in arm: every constant is a constant expression.  Derived static transforms:
 //   J0   = A0 * AJ[0]                joint_0 frame (independent of q)
 //   S[i] = B[i] * AJ[i+1]            joint_i (after Rz(q_i)) -> joint_{i+1}
@@ -320,6 +327,17 @@ struct StaticArm {
   static constexpr double BE(int e) { return kHasEE ? aff_mul(Tab::B[N - 1], Tab::E, e) : Tab::B[N - 1][e]; }
   static constexpr double A0m(int e) { return Tab::A0[e]; }
   static constexpr double MD(int l, int r) { return Tab::MD[l][r]; }
+  // general-inertia arms: what the world-frame diagonals MD leave out - the off-diagonal remainder of the full link
+  // inertia, O_l = ML[l] - diag(MD[l]), and the joint (motor / rotor) inertias MJ[j]; 6x6 row-major, e = r * 6 + c
+  static constexpr bool kGI = tab_gi<Tab>::value;
+  static constexpr double GIL(int l, int e) {
+    if constexpr (kGI) return Tab::ML[l][e] - (e / 6 == e % 6 ? Tab::MD[l][e / 6] : 0.0);
+    else return 0.0;
+  }
+  static constexpr double GIJ(int j, int e) {
+    if constexpr (kGI) return Tab::MJ[j][e];
+    else return 0.0;
+  }
   // angular inertia seen by joint pair with max index m: sum of links l > m (l < NL)
   static constexpr double Isuf(int m, int r) {
     double s = 0.0;
@@ -366,6 +384,7 @@ template <int NJ, class T>
 struct RtArm {
   static constexpr int N = NJ;
   static constexpr bool kStatic = false;
+  static constexpr bool kGI = false;  // general inertias are for compiled arms only (StaticArm)
   static constexpr bool kOrtho = false;  // always differentiate the general affine chain
   static constexpr bool kOrthoFrames = false;
   static constexpr bool kPlanar = false;
@@ -410,6 +429,8 @@ ABRK_ACC(AccBE, A::BE(idx_pack<Ix...>::v[0]), a.BEv[idx_pack<Ix...>::v[0]])
 ABRK_ACC(AccA0, A::A0m(idx_pack<Ix...>::v[0]), a.A0v[idx_pack<Ix...>::v[0]])
 ABRK_ACC(AccMD, A::MD(idx_pack<Ix...>::v[0], idx_pack<Ix...>::v[1]), a.MDv[idx_pack<Ix...>::v[0]][idx_pack<Ix...>::v[1]])
 ABRK_ACC(AccIsuf, A::Isuf(idx_pack<Ix...>::v[0], idx_pack<Ix...>::v[1]), a.Isufv[idx_pack<Ix...>::v[0]][idx_pack<Ix...>::v[1]])
+ABRK_ACC(AccGIL, A::GIL(idx_pack<Ix...>::v[0], idx_pack<Ix...>::v[1]), T(0))
+ABRK_ACC(AccGIJ, A::GIJ(idx_pack<Ix...>::v[0], idx_pack<Ix...>::v[1]), T(0))
 
 // acc + coef*x with compile-time folding of coef in {0, 1, -1}.  Start accumulators at
 // -0.0 (additive identity that LLVM folds exactly under strict IEEE).
@@ -661,8 +682,9 @@ struct Dyn {
   T bw[3], bal[3], bao[3];
 };
 // the recursive Coriolis-vector path (below) replaces the omega prefix sums
+// (general-inertia arms take the per-link form: their extra terms are not in the recursion)
 template <class A, int CM>
-constexpr bool kRecursiveC = (CM == CMODE_VEC) && A::kOrtho;
+constexpr bool kRecursiveC = (CM == CMODE_VEC) && A::kOrtho && !A::kGI;
 
 // does link L carry linear / any mass?  (static arms: compile time; user arms: assume yes)
 template <class A, int L>
@@ -835,7 +857,7 @@ ABRK_INL void angular_finish(const A& arm, const Joints<A, T>& jt, const T (&dq)
   });
   // (orthogonal chains in CMODE_VEC: the angular Coriolis vector is accumulated link by link in
   //  angular_link_coriolis during the forward pass)
-  if constexpr (CM == CMODE_VEC && !A::kOrtho) {
+  if constexpr (CM == CMODE_VEC && !kRecursiveC<A, CM>) {
     // general affine chain: c^w_k = zdot_k.y_k + z_k.y'_k - sum_{i>k} dq_i (W_k z_i).y_i
     //   y_k  = sum_i Ibar_max(k,i) o (z_i dq_i),   y'_k = sum_i Ibar_max(k,i) o (zdot_i dq_i)
     T zd[N][3];
@@ -888,6 +910,128 @@ ABRK_INL void angular_finish(const A& arm, const Joints<A, T>& jt, const T (&dq)
         d.Cm[k() * N + j()] += T(0.5) * acc;
       });
     });
+  }
+}
+
+// General-inertia arms (A::kGI): the contribution of one frame that carries a constant, symmetric 6x6 inertia I in
+// the world frame (the reference applies _M_LINKS / _M_JOINTS unrotated, base_config.py:449-455, 626-632), at point p
+// and moved by joints 0..MC-1.  Its Jacobian columns are J_i = (W_i (p - o_i); z_i), and with Y_i = I J_i:
+//   M_ij += J_i . Y_j,    gz_i += Y_i[2]                       (g = J^T I (0, 0, -9.81, 0, 0, 0))
+// The Christoffel symbols of J^T I J need the time derivatives of the columns and their "transposed" sums
+//   Jdot_i = (W_i sum_{k>=i} Jv_k dq_k + Omega_i Jv_i;  Omega_i z_i),     gw_i = W_i s_i,  s_i = sum_{i<k<MC} dq_k z_k
+//   h_i    = Omega_i z_i - gw_i        (angular; the linear second derivatives are symmetric and cancel)
+// and give (derivation in DESIGN.md, "General inertias"):
+//   CMODE_VEC:  c_k  += J_k . I a + h_k . (I v)_ang,         v = J dq,  a = Jdot dq
+//   CMODE_MAT:  C_kj += 1/2 (h_k . Y_j,ang + Y_k . P_j + (I v)_ang . D_jk)
+//               P_j = (2 Jdot_v,j; Omega_j z_j + gw_j),  D_jk = [j<k] W_j z_k - [k<j] W_k z_j
+// Acc<A, T, F, e> is the inertia element e = r * 6 + c of frame F (compile-time constants: zeros fold away).
+template <int MC, template <class, class, int...> class Acc, int F, class A, class T, int CM>
+ABRK_INL void gi_frame(const A& arm, const Joints<A, T>& jt, const T (&dq)[A::N], const T (&p)[3], Dyn<A, T, CM>& d) {
+  if constexpr (MC > 0) {
+    constexpr int N = A::N;
+    T J[MC][6], Y[MC][6];
+    sfor<MC>([&](auto i) ABRK_LAMBDA {
+      T dlt[3] = {p[0] - jt.o[i()][0], p[1] - jt.o[i()][1], p[2] - jt.o[i()][2]};
+      T e[3];
+      wapply<i()>(jt, dlt, e);
+      sfor<3>([&](auto r) ABRK_LAMBDA {
+        J[i()][r()] = e[r()];
+        J[i()][3 + r()] = jt.z[i()][r()];
+      });
+    });
+    // I x for a 6-vector x
+    auto imul = [&](const T(&x)[6], T(&o)[6]) ABRK_LAMBDA {
+      sfor<6>([&](auto r) ABRK_LAMBDA {
+        T acc = T(-0.0);
+        sfor<6>([&](auto c) ABRK_LAMBDA { acc = cfma<Acc<A, T, F, r() * 6 + c()>>(arm, x[c()], acc); });
+        o[r()] = acc;
+      });
+    };
+    auto dot6 = [&](const T(&x)[6], const T(&y)[6]) ABRK_LAMBDA -> T {
+      T acc = T(-0.0);
+      sfor<6>([&](auto r) ABRK_LAMBDA { acc = Rm<T>::fma(x[r()], y[r()], acc); });
+      return acc;
+    };
+    sfor<MC>([&](auto i) ABRK_LAMBDA { imul(J[i()], Y[i()]); });
+    sfor<MC>([&](auto i) ABRK_LAMBDA {
+      d.gz[i()] += Y[i()][2];
+      sfor<i() + 1>([&](auto j) ABRK_LAMBDA { d.Ms[tri(i(), j())] += dot6(J[i()], Y[j()]); });
+    });
+    if constexpr (CM != CMODE_NONE) {
+      T Jd[MC][6], h[MC][3], gw[MC][3];
+      T sl[3] = {T(-0.0), T(-0.0), T(-0.0)}, sw[3] = {T(-0.0), T(-0.0), T(-0.0)};
+      sfor<MC>([&](auto ir) ABRK_LAMBDA {
+        constexpr int i = MC - 1 - ir();
+        // gw_i = W_i sum_{k>i} dq_k z_k (sw before adding joint i), then the suffix sums take column i
+        wapply<i>(jt, sw, gw[i]);
+        sfor<3>([&](auto r) ABRK_LAMBDA {
+          sl[r()] += J[i][r()] * dq[i];
+          sw[r()] += jt.z[i][r()] * dq[i];
+        });
+        T t1[3], t2[3], oz[3];
+        wapply<i>(jt, sl, t1);
+        const T jv[3] = {J[i][0], J[i][1], J[i][2]};
+        omega_apply<i>(jt, d, dq, jv, t2);
+        omega_apply<i>(jt, d, dq, jt.z[i], oz);
+        sfor<3>([&](auto r) ABRK_LAMBDA {
+          Jd[i][r()] = t1[r()] + t2[r()];
+          Jd[i][3 + r()] = oz[r()];
+          h[i][r()] = oz[r()] - gw[i][r()];
+        });
+      });
+      T v[6], Iv[6];
+      sfor<6>([&](auto r) ABRK_LAMBDA {
+        T acc = T(-0.0);
+        sfor<MC>([&](auto i) ABRK_LAMBDA { acc = Rm<T>::fma(J[i()][r()], dq[i()], acc); });
+        v[r()] = acc;
+      });
+      imul(v, Iv);
+      if constexpr (CM == CMODE_VEC) {
+        T a[6], Ia[6];
+        sfor<6>([&](auto r) ABRK_LAMBDA {
+          T acc = T(-0.0);
+          sfor<MC>([&](auto i) ABRK_LAMBDA { acc = Rm<T>::fma(Jd[i()][r()], dq[i()], acc); });
+          a[r()] = acc;
+        });
+        imul(a, Ia);
+        sfor<MC>([&](auto k) ABRK_LAMBDA {
+          T acc = dot6(J[k()], Ia);
+          sfor<3>([&](auto r) ABRK_LAMBDA { acc = Rm<T>::fma(h[k()][r()], Iv[3 + r()], acc); });
+          d.cv[k()] += acc;
+        });
+      } else {
+        sfor<MC>([&](auto j) ABRK_LAMBDA {
+          T P[6];
+          sfor<3>([&](auto r) ABRK_LAMBDA {
+            P[r()] = T(2) * Jd[j()][r()];
+            P[3 + r()] = Jd[j()][3 + r()] + gw[j()][r()];
+          });
+          sfor<MC>([&](auto k) ABRK_LAMBDA {
+            T acc = dot6(Y[k()], P);
+            sfor<3>([&](auto r) ABRK_LAMBDA { acc = Rm<T>::fma(h[k()][r()], Y[j()][3 + r()], acc); });
+            if constexpr (j() != k()) {
+              constexpr int lo = j() < k() ? j() : k(), hi = j() < k() ? k() : j();
+              T x[3];
+              wapply<lo>(jt, jt.z[hi], x);  // W_lo z_hi, with the sign of D_jk
+              const T dd = Iv[3] * x[0] + Iv[4] * x[1] + Iv[5] * x[2];
+              acc = j() < k() ? acc + dd : acc - dd;
+            }
+            d.Cm[k() * N + j()] += T(0.5) * acc;
+          });
+        });
+      }
+    }
+  }
+}
+
+// the general-inertia terms of link L and of joint frame L - 1, from the link visitor of the forward kinematics (joint
+// L - 1 has just been recorded; p is the centre of mass of link L)
+template <int L, class A, class T, int CM>
+ABRK_INL void gi_accumulate(const A& arm, const Joints<A, T>& jt, const T (&dq)[A::N], const T (&p)[3],
+                            Dyn<A, T, CM>& d) {
+  if constexpr (A::kGI && L - 1 < A::N) {
+    if constexpr (L < A::NL) gi_frame<L, AccGIL, L>(arm, jt, dq, p, d);
+    gi_frame<L - 1, AccGIJ, L - 1>(arm, jt, dq, jt.o[L - 1], d);
   }
 }
 
@@ -1158,6 +1302,7 @@ ABRK_INL void kin_dyn_hook(const A& arm, const T (&q)[A::N], const T (&dq)[A::N]
     body_advance<L()>(jt, dq, d);
     link_accumulate<L()>(arm, jt, dq, p, d);
     angular_link_coriolis<L()>(arm, jt, d);
+    gi_accumulate<L()>(arm, jt, dq, p, d);
     extra(L, p);
   };
   if constexpr (std::is_same<Sc, ScTab>::value) {

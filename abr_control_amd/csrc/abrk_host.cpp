@@ -72,12 +72,14 @@ struct ArmEntry {
   const ArmOps* ops = nullptr;
   std::vector<unsigned char> rt64, rt32;  // RtArm<N,double> / RtArm<N,float> images (user arms on the runtime-table
                                           // kernels; empty for built-in and compiled arms)
+  std::shared_ptr<const abrk_arm_inertia> gi;  // full inertias of a general-inertia compiled arm; null: the plain form
 };
 // plugins stay loaded for the life of the process (their code objects are registered with the HIP runtime)
 struct PluginLib {
   std::string path;
   const ArmOps* ops;
   abrk_arm_desc desc;
+  std::shared_ptr<const abrk_arm_inertia> inertia;
 };
 std::vector<PluginLib> g_plugins;
 std::mutex g_mu;
@@ -174,9 +176,25 @@ bool same_table(const abrk_arm_desc& a, const abrk_arm_desc& b) {
 }
 }  // namespace
 
+namespace {
+// the inertias of links 0..n and joints 0..n-1 agree value by value
+bool same_inertia(const abrk_arm_inertia& a, const abrk_arm_inertia& b, int n) {
+  for (int l = 0; l <= n; l++)
+    if (memcmp(a.mlink[l], b.mlink[l], sizeof a.mlink[l])) return false;
+  for (int j = 0; j < n; j++)
+    if (memcmp(a.mjoint[j], b.mjoint[j], sizeof a.mjoint[j])) return false;
+  return true;
+}
+}  // namespace
+
 extern "C" const char* abrk_plugin_abi(void) { return ABRK_PLUGIN_ABI; }
 
 extern "C" int abrk_arm_create_compiled(const abrk_arm_desc* d, const char* plugin_path) {
+  return abrk_arm_create_compiled_inertia(d, nullptr, plugin_path);
+}
+
+extern "C" int abrk_arm_create_compiled_inertia(const abrk_arm_desc* d, const abrk_arm_inertia* inertia,
+                                                const char* plugin_path) {
   if (!d || !plugin_path) return fail(ABRK_EINVAL, "abrk_arm_create_compiled: NULL argument");
   if (d->n_joints < 1 || d->n_joints > ABRK_MAX_JOINTS)
     return fail(ABRK_EINVAL, "n_joints=%d outside 1..%d", d->n_joints, ABRK_MAX_JOINTS);
@@ -193,6 +211,7 @@ extern "C" int abrk_arm_create_compiled(const abrk_arm_desc* d, const char* plug
     auto f_abi = reinterpret_cast<abrk_plugin_abi_fn>(dlsym(h, "abrk_plugin_abi_tag"));
     auto f_ops = reinterpret_cast<abrk_plugin_ops_fn>(dlsym(h, "abrk_plugin_ops"));
     auto f_desc = reinterpret_cast<abrk_plugin_desc_fn>(dlsym(h, "abrk_plugin_desc"));
+    auto f_inertia = reinterpret_cast<abrk_plugin_inertia_fn>(dlsym(h, "abrk_plugin_inertia"));
     if (!f_abi || !f_ops || !f_desc) {
       dlclose(h);
       return fail(ABRK_EINVAL, "%s is not an arm plugin (entry points missing)", plugin_path);
@@ -203,15 +222,28 @@ extern "C" int abrk_arm_create_compiled(const abrk_arm_desc* d, const char* plug
       dlclose(h);
       return rc;
     }
+    if (!f_inertia) {  // (same headers, so never for a plugin that make built)
+      dlclose(h);
+      return fail(ABRK_EINVAL, "%s is not an arm plugin (entry points missing)", plugin_path);
+    }
     PluginLib p;
     p.path = plugin_path;
     p.ops = static_cast<const ArmOps*>(f_ops());
     f_desc(&p.desc);
+    auto in = std::make_shared<abrk_arm_inertia>();
+    f_inertia(in.get());
+    p.inertia = in;
     g_plugins.push_back(std::move(p));
     pl = &g_plugins.back();
   }
   if (!same_table(pl->desc, *d))
     return fail(ABRK_EINVAL, "arm plugin %s was compiled for a different arm table than the one given", plugin_path);
+  abrk_arm_inertia plain;
+  inertia_plain(*d, &plain);
+  const bool gi = !same_inertia(*pl->inertia, plain, d->n_joints);
+  if (!same_inertia(*pl->inertia, inertia ? *inertia : plain, d->n_joints))
+    return fail(ABRK_EINVAL, "arm plugin %s was compiled for %s inertias than the ones given", plugin_path,
+                gi ? "other (general)" : "other (plain)");
   int slot = -1;
   for (int i = 5; i < (int)g_arms.size() && slot < 0; i++)
     if (!g_arms[i].live) slot = i;
@@ -221,6 +253,7 @@ extern "C" int abrk_arm_create_compiled(const abrk_arm_desc* d, const char* plug
   e.desc = *d;
   e.desc.name[sizeof e.desc.name - 1] = 0;
   e.ops = pl->ops;
+  if (gi) e.gi = pl->inertia;
   if (slot >= 0) {
     e.gen = g_arms[slot].gen;
     g_arms[slot] = std::move(e);
@@ -237,6 +270,14 @@ extern "C" int abrk_arm_get_desc(int arm_id, abrk_arm_desc* out) {
   return 0;
 }
 
+extern "C" int abrk_arm_get_inertia(int arm_id, abrk_arm_inertia* out) {
+  ArmEntry* a = get_arm(arm_id);
+  if (!a || !out) return fail(ABRK_ENOARM, "unknown arm id %d", arm_id);
+  if (a->gi) *out = *a->gi;
+  else inertia_plain(a->desc, out);
+  return 0;
+}
+
 extern "C" int abrk_arm_destroy(int arm_id) {
   std::lock_guard<std::mutex> lk(g_mu);
   init_builtins();
@@ -246,6 +287,7 @@ extern "C" int abrk_arm_destroy(int arm_id) {
   g_arms[slot].gen = (g_arms[slot].gen + 1) & kArmGenMask;
   g_arms[slot].rt64 = {};
   g_arms[slot].rt32 = {};
+  g_arms[slot].gi = nullptr;
   return 0;
 }
 

@@ -190,6 +190,10 @@ static_assert(kWlBlock == kBlock, "wl_capacity assumes one first-pass workgroup 
 constexpr unsigned kKm6GridCap = 4096;  // one-wave first pass of the six-row law: a persistent grid of at most this many blocks (a multiple of kWlLists)
 // the first pass of the six-row law as one row per lane (no persistent grid): where it holds two waves per SIMD - a
 // one-wave first pass (general chains) keeps the loop, whose next row hides the stores of the last
+// the OSC kernels' register budget and Coriolis form follow the chain: an orthogonal one takes the body recursion (two
+// waves per SIMD) - except on general-inertia arms, whose extra terms ride on the per-link form of general chains
+template <class A>
+constexpr bool osc_ortho() { return A::kOrtho && !A::kGI; }
 constexpr bool km6_first_pass_plain(int km, bool use_c, int feat, bool ortho, int pass, bool is_static) {
   return km == 6 && pass == 1 && osc_min_waves(km, use_c, feat, ortho, pass, is_static) >= 2;
 }
@@ -209,12 +213,12 @@ constexpr bool km6_first_pass_plain(int km, bool use_c, int feat, bool ortho, in
 // cost the config-sized step 3-4 % (profiles/round4/mw_ab.txt).  The form was removed in round 5.
 template <class A, class T, int KM, bool USE_C>
 constexpr bool osc_uses_slab() {
-  return (USE_C && A::kOrtho) || KM == 6;
+  return (USE_C && osc_ortho<A>()) || KM == 6;
 }
 // EEF (the plain six-row law of arms with a two-wave first pass): the launch's ref_frame is the end effector -
 // ScratchBase::kEeFrame.
 template <class A, class T, int KM, bool USE_C, int FEAT, int PASS = 0, bool NOTS = false, bool EEF = false>
-__global__ void __launch_bounds__(kBlock, osc_min_waves(KM, USE_C, FEAT, A::kOrtho, PASS, A::kStatic))
+__global__ void __launch_bounds__(kBlock, osc_min_waves(KM, USE_C, FEAT, osc_ortho<A>(), PASS, A::kStatic))
 osc_kernel(A arm, OscP<T> P, long B, const T* __restrict__ qg, const T* __restrict__ dqg,
            const T* __restrict__ tg, const T* __restrict__ tvg, T* __restrict__ ierrg,
            const T* __restrict__ uneg, T* __restrict__ ug, T* __restrict__ tsg, int mode, int* __restrict__ wl,
@@ -290,7 +294,7 @@ osc_kernel(A arm, OscP<T> P, long B, const T* __restrict__ qg, const T* __restri
       return scr.deferred;
     };
     static_assert(!NOTS || (KM == 6 && FEAT == 0), "NOTS is instantiated for the plain six-row law");
-    static_assert(!EEF || (A::kOrtho && KM == 6 && FEAT == 0 && km6_first_pass_plain(KM, USE_C, FEAT, A::kOrtho, 1, A::kStatic)),
+    static_assert(!EEF || (osc_ortho<A>() && KM == 6 && FEAT == 0 && km6_first_pass_plain(KM, USE_C, FEAT, osc_ortho<A>(), 1, A::kStatic)),
                   "EEF is instantiated for the plain six-row law of arms with a two-wave first pass");
     using S0 = std::conditional_t<kLds, LdsScratch<T, A::N>, TabScratch<T, A::N>>;
     using S1 = std::conditional_t<PASS == 1, DeferOnly<S0>, S0>;
@@ -311,7 +315,7 @@ osc_kernel(A arm, OscP<T> P, long B, const T* __restrict__ qg, const T* __restri
       if (threadIdx.x == 0) reinterpret_cast<unsigned long long*>(wl)[b / kBlock] = m;
     }
   };
-  if constexpr (km6_first_pass_plain(KM, USE_C, FEAT, A::kOrtho, PASS, A::kStatic)) {
+  if constexpr (km6_first_pass_plain(KM, USE_C, FEAT, osc_ortho<A>(), PASS, A::kStatic)) {
     // first pass at two waves per SIMD: one row per lane, no loop.  The second wavefront of the SIMD hides a row's
     // memory round trips, and outside a loop nothing is hoisted: in the persistent-loop form the compiler keeps the
     // row program's literals and the controller's parameters in scalar registers across iterations, runs out of them
@@ -480,7 +484,7 @@ constexpr long kHandoverMaxRows = 262144;  // (the finish kernel's grid: 4096 ch
 // parked.  FEAT is 0 (the plain law) or 2 (every optional input).
 // (the C / dJ variant is not capped at 256 registers: that costs 364-424 B of scratch, measured in round 3)
 template <class A, class T, int KM, bool USE_C, int FEAT, bool VEL = false>
-__global__ void __launch_bounds__(kBlock, VEL ? kMinWaves : osc_min_waves(KM, USE_C, FEAT, A::kOrtho, 0, A::kStatic))
+__global__ void __launch_bounds__(kBlock, VEL ? kMinWaves : osc_min_waves(KM, USE_C, FEAT, osc_ortho<A>(), 0, A::kStatic))
 osc_full_kernel(A arm, OscP<T> P, long B, const T* __restrict__ qg, const T* __restrict__ dqg,
                 const T* __restrict__ tg, const T* __restrict__ tvg, T* __restrict__ ierrg,
                 const T* __restrict__ uneg, T* __restrict__ ug, T* __restrict__ tsg, unsigned want, DynOutP<T> out) {
@@ -492,7 +496,7 @@ osc_full_kernel(A arm, OscP<T> P, long B, const T* __restrict__ qg, const T* __r
   LdsStore<T> st{slab, row0, B, (int)threadIdx.x};
   __shared__ T sctab[2 * kSinCosN];
   load_sincos_table(sctab, (int)threadIdx.x);
-  if constexpr ((USE_C && !VEL && A::kOrtho) || KM == 6) {
+  if constexpr ((USE_C && !VEL && osc_ortho<A>()) || KM == 6) {
     using V2 = typename LdsScratch<T, A::N>::V2;
     LdsScratch<T, A::N> scr;
     scr.slab = reinterpret_cast<V2*>(slab);
@@ -828,7 +832,8 @@ struct Launch {
     // pass of such a launch takes the EEF form (first pass, recompute pass, one-pass): the capture changes the basic-block
     // structure of the forward kinematics, and with it which multiply the compiler fuses with which add in its
     // `c a0 + s a1` shapes - a row's bits must not depend on the pass that evaluates it.
-    constexpr bool kEefBuilt = A::kOrtho && km6_first_pass_plain(KM, UC, FEAT, A::kOrtho, 1, A::kStatic);
+    // (general-inertia arms keep the capture too: the EEF form was measured on plain chains only)
+    constexpr bool kEefBuilt = osc_ortho<A>() && km6_first_pass_plain(KM, UC, FEAT, osc_ortho<A>(), 1, A::kStatic);
     const bool eef = kEefBuilt && static_cast<const OscP<T>*>(a.P)->ref_frame == 2 * A::N + 1;
     auto launch = [&](auto pass, auto nots_, auto eef_, dim3 grid, int mode) {
       hipLaunchKernelGGL((osc_kernel<A, T, KM, UC, FEAT, pass(), nots_(), eef_()>), grid, dim3(kBlock), 0, la.stream,
@@ -864,7 +869,7 @@ struct Launch {
           if (hipError_t e = hipMemsetAsync(a.wl, 0, 16 * kWlLists * sizeof(int), la.stream); e != hipSuccess) return e;
         dim3 g1 = grid_for(la.B);
         // (the persistent-grid form of the first pass: a multiple of kWlLists)
-        constexpr bool plain = km6_first_pass_plain(KM, UC, FEAT, A::kOrtho, 1, A::kStatic);
+        constexpr bool plain = km6_first_pass_plain(KM, UC, FEAT, osc_ortho<A>(), 1, A::kStatic);
         if (!plain && g1.x > kKm6GridCap) g1.x = kKm6GridCap;
         if (nots) go_nots(ic<1>{}, g1, 1);
         else go(ic<1>{}, g1, 1);

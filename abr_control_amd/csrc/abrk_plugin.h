@@ -13,6 +13,7 @@
 #include <cstring>
 
 #include "../../include/abrk_types.h"
+#include "abrk_device.h"  // tab_gi
 
 #ifndef ABRK_PLUGIN_ABI
 #error "ABRK_PLUGIN_ABI (hash of the kernel headers, set by the Makefile) is not defined"
@@ -36,6 +37,23 @@ void desc_from_tab(abrk_arm_desc* d) {
   for (int l = 0; l <= Tab::N; l++) memcpy(d->mdiag[l], Tab::MD[l], 6 * sizeof(double));
   snprintf(d->name, sizeof d->name, "%s", Tab::kName);
 }
+// the plain form of a description: diagonal link inertias, no joint inertias
+inline void inertia_plain(const abrk_arm_desc& d, abrk_arm_inertia* o) {
+  memset(o, 0, sizeof *o);
+  for (int l = 0; l <= d.n_joints && l <= ABRK_MAX_JOINTS; l++)
+    for (int r = 0; r < 6; r++) o->mlink[l][r * 7] = d.mdiag[l][r];
+}
+// the inertias a compile-time table stands for (StaticArm::kGI tables carry them; every other is plain)
+template <class Tab>
+void inertia_from_tab(abrk_arm_inertia* o) {
+  abrk_arm_desc d;
+  desc_from_tab<Tab>(&d);
+  inertia_plain(d, o);
+  if constexpr (tab_gi<Tab>::value) {
+    for (int l = 0; l <= Tab::N; l++) memcpy(o->mlink[l], Tab::ML[l], sizeof o->mlink[l]);
+    for (int j = 0; j < Tab::N; j++) memcpy(o->mjoint[j], Tab::MJ[j], sizeof o->mjoint[j]);
+  }
+}
 }  // namespace abrk
 
 // entry points of a plugin (resolved with dlsym by abrk_arm_create_compiled)
@@ -43,6 +61,7 @@ extern "C" {
 typedef const void* (*abrk_plugin_ops_fn)(void);         // -> const abrk::ArmOps*
 typedef const char* (*abrk_plugin_abi_fn)(void);         // must equal libabrk's ABRK_PLUGIN_ABI
 typedef void (*abrk_plugin_desc_fn)(abrk_arm_desc* out);  // the table the kernels were compiled for
+typedef void (*abrk_plugin_inertia_fn)(abrk_arm_inertia* out);  // ... and its inertias (the plain form if it has none)
 }
 
 #ifdef ABRK_PLUGIN_BODY
@@ -54,5 +73,8 @@ extern "C" __attribute__((visibility("default"))) const void* abrk_plugin_ops(vo
 extern "C" __attribute__((visibility("default"))) const char* abrk_plugin_abi_tag(void) { return ABRK_PLUGIN_ABI; }
 extern "C" __attribute__((visibility("default"))) void abrk_plugin_desc(abrk_arm_desc* out) {
   abrk::desc_from_tab<abrk::ABRK_PLUGIN_TAB>(out);
+}
+extern "C" __attribute__((visibility("default"))) void abrk_plugin_inertia(abrk_arm_inertia* out) {
+  abrk::inertia_from_tab<abrk::ABRK_PLUGIN_TAB>(out);
 }
 #endif

@@ -56,6 +56,15 @@ int abrk_arm_create(const abrk_arm_desc* desc);
  * refused with ABRK_EINVAL on any mismatch.  The arm then runs the same compile-time specialised kernels as a built-in
  * arm (about 2.2x the rate of the runtime-table kernels abrk_arm_create gives).  Returns arm id >= 0.                */
 int abrk_arm_create_compiled(const abrk_arm_desc* desc, const char* plugin_path);
+/* The same for an arm with full link inertias and joint inertias (abrk_types.h abrk_arm_inertia): `inertia` is checked
+ * value by value against the one the plugin was compiled for, like `desc`.  NULL stands for the plain form of `desc`
+ * (diagonal link inertias, no joint inertias), i.e. abrk_arm_create_compiled.  General inertias run on compiled arms
+ * only: abrk_arm_create has no inertia argument.  Returns arm id >= 0.                                                  */
+int abrk_arm_create_compiled_inertia(const abrk_arm_desc* desc, const abrk_arm_inertia* inertia,
+                                     const char* plugin_path);
+/* the inertias an arm runs with: the plain form (diag(mdiag), zero joint inertias) for every arm but a general-inertia
+ * compiled one                                                                                                        */
+int abrk_arm_get_inertia(int arm_id, abrk_arm_inertia* out);
 /* tag of the kernel headers and compile flags this library was built from; a plugin must carry the same one */
 const char* abrk_plugin_abi(void);
 int abrk_arm_get_desc(int arm_id, abrk_arm_desc* out);

@@ -67,4 +67,17 @@ typedef struct abrk_arm_desc {
   char name[32];
 } abrk_arm_desc;
 
+/* ---------------------------------------------------------------------------------
+ * Full inertias of a general-inertia arm (compiled arms only, abrk_arm_create_compiled_inertia): the reference's
+ * 6x6 `_M_LINKS[l]` (base_config.py:449-451, 626-628) and `_M_JOINTS[j]` - motor / rotor inertias, applied through the
+ * Jacobian of the joint frame (:452-455, 629-632) - row-major, in the WORLD frame like mdiag.  Matrices are symmetric.
+ * mlink[l] for l < n_links_dyn counts; its diagonal is mdiag[l] (the kernels add the off-diagonal remainder).  Joint
+ * frame j moves with joints 0..j-1 only, so mjoint[0] contributes nothing, as in the reference.
+ * A plain arm's inertia is diag(mdiag[l]) per link and zero per joint.
+ * --------------------------------------------------------------------------------- */
+typedef struct abrk_arm_inertia {
+  double mlink[ABRK_MAX_JOINTS + 1][36];
+  double mjoint[ABRK_MAX_JOINTS][36];
+} abrk_arm_inertia;
+
 #endif /* ABRK_TYPES_H */

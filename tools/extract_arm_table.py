@@ -7,6 +7,10 @@ instead of SymPy code generation + Cython compilation on first use
 (abr_control/arms/base_config.py:125-146), the arm's frame chain is reduced once to a
 small table of static transforms that the HIP kernels consume.
 
+Inertias: `mdiag` holds the diagonals of `_M_LINKS`; an arm whose link inertias are not diagonal gets `mlink` (the full
+matrices) and one with non-zero `_M_JOINTS` gets `mjoint` as well - general-inertia arms, which run on compiled kernels
+(abr_control_amd/specialize.py).  Asymmetric matrices are refused.
+
 Assumed chain structure (true for every arm the reference ships, e.g.
 abr_control/arms/ur5/config.py:301-339):
     T(link0)    = A0
@@ -89,20 +93,28 @@ def extract(rc, name=None):
                 raise ValueError("frame chain is not of the link/joint/Rz form this tool supports")
     A0, AJ, B, E = tables[0]
 
-    mdiag = []
-    for l in range(n + 1):
-        if l < len(rc._M_LINKS):
-            Ml = np.array(sp.Matrix(rc._M_LINKS[l]).tolist(), dtype=float)
-            if not np.allclose(Ml, np.diag(np.diag(Ml))):
-                raise ValueError(f"_M_LINKS[{l}] is not diagonal - unsupported")
-            mdiag.append([float(v) for v in np.diag(Ml)])
-        else:
-            mdiag.append([0.0] * 6)
-    for Mj in rc._M_JOINTS:
-        if np.any(np.array(sp.Matrix(Mj).tolist(), dtype=float) != 0):
-            raise ValueError("non-zero _M_JOINTS are not supported")
+    def inertia(M, what):
+        M = np.array(sp.Matrix(M).tolist(), dtype=float)
+        if M.shape != (6, 6):
+            raise ValueError(f"{what} is not 6x6")
+        if not np.array_equal(M, M.T):
+            raise ValueError(f"{what} is not symmetric")
+        return M
+
+    mlink = [inertia(rc._M_LINKS[l], f"_M_LINKS[{l}]") if l < len(rc._M_LINKS) else np.zeros((6, 6))
+             for l in range(n + 1)]
+    mjoint = [inertia(rc._M_JOINTS[j], f"_M_JOINTS[{j}]") if j < len(rc._M_JOINTS) else np.zeros((6, 6))
+              for j in range(n)]
+    mdiag = [[float(v) for v in np.diag(M)] for M in mlink]
 
     has_ee = not np.allclose(E, np.eye(4), rtol=0, atol=1e-12)
+    # full inertias (include/abrk_types.h abrk_arm_inertia) only where the diagonals do not say everything: compiled
+    # arms run them (abr_control_amd/_abi.py normalize_table)
+    extra = {}
+    if any(np.any(M != np.diag(np.diag(M))) for M in mlink):
+        extra["mlink"] = [M.tolist() for M in mlink]
+    if any(np.any(M != 0) for M in mjoint):
+        extra["mjoint"] = [M.tolist() for M in mjoint]
     return {
         "name": name or getattr(rc, "ROBOT_NAME", "robot"),
         "n_joints": n,
@@ -113,6 +125,7 @@ def extract(rc, name=None):
         "B": [_snapm(m) for m in B],
         "E": _snapm(E),
         "mdiag": mdiag,
+        **extra,
         "START_ANGLES": [float(v) for v in np.asarray(rc.START_ANGLES, dtype=float)],
     }
 
