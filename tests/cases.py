@@ -254,16 +254,19 @@ class HostsimBackend:
 class GpuBackend:
     """libabrk.so through the C ABI (abr_control_amd.engine) - static or runtime-table arm"""
 
-    # rows per call of the forms of the six-row law (abrk_host.cpp: one pass below one wavefront of rows, hand-over
-    # records + finish kernel up to 65 536 rows, worklist + recompute pass beyond)
-    ONE_PASS_ROWS, RECOMPUTE_ROWS = 48, 65536 + 128
+    # rows per call of the forms of the six-row law (abrk_host.cpp worklist_for / finish_group_for: one pass below one
+    # wavefront of rows; hand-over records + per-chunk or grouped finish kernel up to 65 536 rows; hand-over records + the
+    # dense finish kernel up to 1 048 576 rows; worklist + recompute pass beyond)
+    ONE_PASS_ROWS, DENSE_ROWS, RECOMPUTE_ROWS = 48, 65536 + 128, (1 << 20) + 128
 
     def __init__(self, arm, variant="static", device=0, training_signal=True, form="auto"):
         """training_signal=False: ask for no training signal - what bench.py times and what a C-ABI caller without that
         buffer gets (the plain six-row law then runs the `NOTS = true` instantiations); osc() returns (u, None).
         form: "auto" = one call on the rows as given; "slices" = calls of ONE_PASS_ROWS rows (the six-row law in one
-        pass: `osc_kernel<.., PASS = 0>` in mode 0); "tiled" = the rows repeated up to RECOMPUTE_ROWS (first pass +
-        recompute pass over the worklist: `PASS = 1` then `PASS = 0` in mode 2), every repetition bit-equal."""
+        pass: `osc_kernel<.., PASS = 0>` in mode 0); "tiled" = the rows repeated up to DENSE_ROWS (first pass on hand-over
+        records, `PASS = 1` in mode 1, then the dense finish kernel, abrk_law.hip osc6_finish_dense_kernel); "recompute" =
+        the rows repeated up to RECOMPUTE_ROWS, beyond 1 M (first pass + recompute pass over the worklist: `PASS = 1` in
+        mode 1, then `PASS = 0` in mode 2).  Tiled forms: every repetition bit-equal."""
         import ctypes as C
 
         from abr_control_amd import engine
@@ -319,8 +322,8 @@ class GpuBackend:
                      for lo in range(0, B, self.ONE_PASS_ROWS)]
             u = np.concatenate([p[0] for p in parts])
             return u, (np.concatenate([p[1] for p in parts]) if self.training_signal else None)
-        assert self.form == "tiled", self.form
-        reps = -(-self.RECOMPUTE_ROWS // B)
+        assert self.form in ("tiled", "recompute"), self.form
+        reps = -(-(self.DENSE_ROWS if self.form == "tiled" else self.RECOMPUTE_ROWS) // B)
         rep = lambda a: None if a is None else np.ascontiguousarray(np.tile(np.asarray(a), (reps, 1)))
         ie_t = rep(ie)
         u, ts = self._osc(params, rep(q), rep(dq), rep(t), rep(tv), ie_t, rep(une), dtype)
@@ -778,6 +781,29 @@ def check_near_singular_postures(backend, arm="ur5", B=600):
     return worst, beyond, trunc
 
 
+def six_row_gate(o, q, ctrlr_dof=SIX, frame="EE", offset=None):
+    """per row of `q`, from the task-space inertia inverse Mx_inv = J M^-1 J^T of the controlled rows (`o` an Oracle):
+    ok - the row is good to TOL_D on both sides in fp64: not within 1e-8 of a threshold of `_Mx` (osc.py:138-145), and the
+    part of Mx_inv the pinv keeps is conditioned below 1e7; trunc - `pinv(Mx_inv, rcond=1e-4)` really drops a singular
+    value (|det| < 1e-3 and min(sv) < 1e-4 max(sv)): the rows the six-row kernels defer to their second pass; cond - the
+    condition number of Mx_inv.  -> (ok, trunc, cond), arrays over the rows"""
+    dof = np.array(ctrlr_dof, bool)
+    B = len(q)
+    ok, trunc, cond = np.ones(B, bool), np.zeros(B, bool), np.zeros(B)
+    for b in range(B):
+        J = o.J(frame, q[b], offset)[dof]
+        A = J @ np.linalg.inv(o.M(q[b])) @ J.T
+        sv = np.linalg.svd(A, compute_uv=False)
+        det = abs(np.linalg.det(A))
+        ratio = sv / sv.max()
+        near = abs(det - 1e-3) < 1e-8 or (det < 1.001e-3 and np.any(np.abs(ratio - 1e-4) < 1e-8))
+        kept = ratio[ratio > 1e-4] if det < 1e-3 else ratio
+        ok[b] = not near and kept.min() > 1e-7
+        trunc[b] = det < 1e-3 and ratio.min() < 1e-4
+        cond[b] = sv.max() / max(sv.min(), 1e-300)
+    return ok, trunc, cond
+
+
 def check_six_row_near_singular(backend, arm="ur5", B=600, reference=None):
     """all six task rows on postures next to the arm's kinematic singularities (near_singular_postures): most of them
     take the truncating pinv(rcond=1e-4) of osc.py:145, i.e. the path the six-row kernels defer to their second pass.
@@ -794,18 +820,7 @@ def check_six_row_near_singular(backend, arm="ur5", B=600, reference=None):
     rng = np.random.RandomState(31)
     dq, t = rng.uniform(-2, 2, (B, n)), rng.uniform(-0.8, 0.8, (B, 6))
     tv, une = rng.uniform(-0.5, 0.5, (B, 6)), rng.uniform(-2, 2, (B, n))
-    ok = np.ones(B, bool)
-    trunc = np.zeros(B, bool)
-    for b in range(B):
-        J = o.J("EE", q[b], None)
-        A = J @ np.linalg.inv(o.M(q[b])) @ J.T
-        sv = np.linalg.svd(A, compute_uv=False)
-        det = abs(np.linalg.det(A))
-        ratio = sv / sv.max()
-        near = abs(det - 1e-3) < 1e-8 or (det < 1.001e-3 and np.any(np.abs(ratio - 1e-4) < 1e-8))
-        kept = ratio[ratio > 1e-4] if det < 1e-3 else ratio
-        ok[b] = not near and kept.min() > 1e-7
-        trunc[b] = det < 1e-3 and ratio.min() < 1e-4
+    ok, trunc, _cond = six_row_gate(o, q)
     assert (ok & trunc).sum() > B // 4, f"too few truncating rows ({(ok & trunc).sum()}/{B})"
     worst = 0.0
     variants = (dict(kw=dict(kp=200, ko=150, kv=25, ctrlr_dof=SIX)),

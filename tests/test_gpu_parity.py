@@ -856,7 +856,7 @@ def test_gpu_six_row_from_threads_on_default_stream():
 NOTS_CASES = [c for c in sorted(cases.CASES) if cases.takes_plain_six_row_law(c)]
 
 
-@pytest.mark.parametrize("form", ["auto", "slices", "tiled"])
+@pytest.mark.parametrize("form", ["auto", "slices", "tiled", "recompute"])
 @pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
 @pytest.mark.parametrize("variant", ["static", "rt"])
 @pytest.mark.parametrize("case_id", NOTS_CASES)
@@ -866,10 +866,12 @@ def test_gpu_six_row_cases_without_training_signal(case_id, variant, dtype, form
     in every pass (Launch::osc_launch) - gravity folded into the velocity term ahead of the factorisations.  Every golden
     case of the plain six-row law (UR5 six rows alg 0 / 1, vmax, orientation only, x-z-beta, link5; Jaco2 five and six
     rows; the three-joint arm's x-y-gamma) against the REFERENCE's outputs with no training signal asked for: built-in and
-    runtime-table kernels, fp64 and fp32, and the three launch forms - "auto": first pass + finish kernel on hand-over
+    runtime-table kernels, fp64 and fp32, and the four launch forms - "auto": first pass + finish kernel on hand-over
     records (`PASS = 1`); "slices": 48-row calls, the complete row program in one pass (`PASS = 0`, mode 0); "tiled":
-    the rows repeated beyond 65 536, first pass + recompute pass over the worklist (`PASS = 1`, then `PASS = 0` in mode 2;
-    every repetition bit-equal).  Reference: controllers/osc.py:294-301, examples/timing_plots.py:36-37."""
+    the rows repeated beyond 65 536, first pass + dense finish kernel on hand-over records (osc6_finish_dense_kernel);
+    "recompute": the rows repeated beyond 1 M, first pass + recompute pass over the worklist (`PASS = 1`, then `PASS = 0`
+    in mode 2).  Tiled forms: every repetition bit-equal.  Reference: controllers/osc.py:294-301,
+    examples/timing_plots.py:36-37."""
     arm = cases.CASES[case_id]["arm"]
     be = cases.GpuBackend(arm, variant, training_signal=False, form=form)
     r = cases.check_case_against_golden(be, case_id, golden(arm), dtype=dtype)
@@ -901,13 +903,14 @@ def test_gpu_fuzz_plain_six_row_law_without_training_signal():
 def test_gpu_compiled_arms_without_training_signal():
     """compiled user-arm plugins (specialize.py) carry their own NOTS instantiations: the three-joint plugin on the
     reference's x-y-gamma cases with no training signal (bit-equal to the built-in arm's kernels, and against the
-    reference's outputs), the four-joint synthetic arm against the oracle - fp64 and fp32, hand-over and one-pass forms"""
+    reference's outputs: hand-over, one-pass, dense-finish and recompute forms), the four-joint synthetic arm against the
+    oracle - fp64 and fp32, hand-over and one-pass forms"""
     from oracle.oracle import Oracle
     from tests import compiled_arms
 
     arms_ = compiled_arms.test_arms()
     g = golden("threejoint")
-    for form in ("auto", "slices", "tiled"):
+    for form in ("auto", "slices", "tiled", "recompute"):
         cu = cases.GpuBackend(arms_["threejoint_user"], "compiled", training_signal=False, form=form)
         bi = cases.GpuBackend("threejoint", training_signal=False, form=form)
         for case_id in ("threejoint:osc_xyg_alg0", "threejoint:osc_xyg_alg1"):
@@ -2219,9 +2222,9 @@ def test_gpu_six_row_deferred_pass_equals_inline_sweeps(variant):
 
 @pytest.mark.parametrize("arm,variant", [("ur5", "static"), ("ur5", "rt"), ("jaco2", "static")])
 def test_gpu_six_row_handover_near_singular_postures(arm, variant):
-    """batches of up to 262144 rows run the six-row law as first pass + finish kernel on hand-over records (a deferring
+    """batches of 64 to 65 536 rows run the six-row law as first pass + finish kernel on hand-over records (a deferring
     row leaves Mx_inv, its task Jacobian rows, u_task and the joint-space sums; osc6_finish_kernel - one deferred row
-    per wavefront, each lane one column - completes it): hundreds of truncating rows (postures next to the kinematic
+    per wavefront, each lane one column - completes it; 600 rows here: the per-chunk kernel): hundreds of truncating rows (postures next to the kinematic
     singularities), plain law / Coriolis + two fused secondary controllers / target velocity + integral state over two
     steps + external null-space signal, against the oracle"""
     be = cases.GpuBackend(arm, variant)
@@ -2347,11 +2350,13 @@ def test_gpu_six_row_many_short_lived_streams():
 
 
 def test_gpu_six_row_bits_do_not_depend_on_the_batch_size():
-    """The six-row law runs one-pass below 64 rows, as first pass + finish kernel on hand-over records up to 65536 rows,
-    as first pass + recompute pass beyond.  Since round 5 every form hands a truncating row to ONE routine
-    (csrc/abrk_ctrl.h osc6_tail) and runs the same arithmetic around it (with and without a training signal among the
-    outputs): a batch just above the 65536-row threshold, its halves, 50-row slices of it (one-pass) and an uneven
-    sharded call return the same bits on every row - and meet the oracle on a sample."""
+    """The six-row law runs one-pass below 64 rows, as first pass + per-chunk or grouped finish kernel on hand-over
+    records up to 65536 rows, as first pass + dense finish kernel on hand-over records up to 1 M rows, and as first pass +
+    recompute pass beyond (that form and the 0.26 - 1 M row band: tests/test_gpu_six_row_large_batches.py).  Since round
+    5 every form hands a truncating row to ONE routine (csrc/abrk_ctrl.h osc6_tail) and runs the same arithmetic around
+    it (with and without a training signal among the outputs): a batch just above the 65536-row threshold (dense finish
+    form), its halves, 50-row slices of it (one-pass) and an uneven sharded call return the same bits on every row - and
+    meet the oracle on a sample."""
     from abr_control_amd import engine
 
     be = cases.GpuBackend("ur5")
@@ -2365,7 +2370,7 @@ def test_gpu_six_row_bits_do_not_depend_on_the_batch_size():
                dict(kp=100, ko=60, kv=12, ctrlr_dof=[1, 1, 1, 1, 1, 0], use_C=True,
                     null_controllers=[_abi.make_damping(5)])):
         p = _abi.make_osc_params(6, **kw)
-        u_big, ts_big = be.osc(p, q, dq, t)                                    # recompute form
+        u_big, ts_big = be.osc(p, q, dq, t)                                    # dense finish form
         u_a, ts_a = be.osc(p, q[:h], dq[:h], t[:h])                            # hand-over form
         u_b, ts_b = be.osc(p, q[h:], dq[h:], t[h:])
         assert np.all(np.isfinite(u_big))
