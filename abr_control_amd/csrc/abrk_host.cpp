@@ -16,6 +16,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/abrk.h"
@@ -547,7 +548,7 @@ thread_local Arena t_arena;
 // over PCIe - one launch and one stream sync instead of 3-4 hipMemcpyAsync calls of a few hundred bytes each.
 // Above ABRK_ZEROCOPY_MAX bytes (default 1 MiB) the copy engine + device scratch arena wins.
 struct PinArena {
-  char* base = nullptr;  // host address
+  char* base = nullptr;  // the memory as the host sees it
   char* dev = nullptr;   // the same memory as the device sees it
   size_t cap = 0;
 };
@@ -575,6 +576,8 @@ void* device_view(const void* p) {
 }
 
 bool recording();  // is this thread inside abrk_plan_begin .. abrk_plan_end?
+// One call per array: bind() fills the kernel argument `field` with the device address of `host` - null stays null, a
+// device-visible pointer is written at once, a pageable host array gets its staging copy's address from reserve().
 struct Stager {
   int device;
   hipStream_t stream;
@@ -583,19 +586,27 @@ struct Stager {
     void* dev;
     size_t bytes;
     bool out, in;
+    void** field;
   };
   std::vector<Item> items;
   size_t need = 0;
   bool staged = false, pinned = false;
 
-  // first pass: register; second pass (after reserve()) resolve
-  void* add(const void* p, size_t bytes, bool in, bool out) {
-    if (!p) return nullptr;
-    if (void* d = device_view(p)) return d;
-    items.push_back({const_cast<void*>(p), nullptr, bytes, out, in});
+  template <class P>
+  void bind(P* field, const void* host, size_t bytes, bool in, bool out) {
+    static_assert(std::is_same<P, void*>::value || std::is_same<P, const void*>::value, "a pointer argument");
+    *field = nullptr;
+    if (!host) return;
+    if (void* d = device_view(host)) {
+      *field = d;
+      return;
+    }
+    items.push_back({const_cast<void*>(host), nullptr, bytes, out, in, const_cast<void**>(field)});
     need += (bytes + 255) & ~size_t(255);
-    return (void*)(uintptr_t)(items.size());  // placeholder index+1, resolved by fix()
   }
+  void in(const void** field, const void* host, size_t bytes) { bind(field, host, bytes, true, false); }
+  void out(void** field, void* host, size_t bytes) { bind(field, host, bytes, false, true); }
+  void inout(void** field, void* host, size_t bytes) { bind(field, host, bytes, true, true); }
   int reserve() {
     if (items.empty()) return 0;
     staged = true;
@@ -623,7 +634,7 @@ struct Stager {
       pinned = true;
       size_t off = 0;
       for (auto& it : items) {
-        it.dev = pa.dev + off;
+        it.dev = *it.field = pa.dev + off;
         if (it.in) memcpy(pa.base + off, it.host, it.bytes);
         off += (it.bytes + 255) & ~size_t(255);
       }
@@ -649,7 +660,7 @@ struct Stager {
     }
     size_t off = 0;
     for (auto& it : items) {
-      it.dev = a.base + off;
+      it.dev = *it.field = a.base + off;
       off += (it.bytes + 255) & ~size_t(255);
       if (it.in) {
         hipError_t e = hipMemcpyAsync(it.dev, it.host, it.bytes, hipMemcpyHostToDevice, stream);
@@ -657,14 +668,6 @@ struct Stager {
       }
     }
     return 0;
-  }
-  // map a value returned by add() to the real device pointer
-  template <class P>
-  P fix(P p, const void* orig) const {
-    if (!orig) return nullptr;
-    for (size_t i = 0; i < items.size(); i++)
-      if (items[i].host == orig && (uintptr_t)p == i + 1) return (P)items[i].dev;
-    return p;
   }
   int finish() {
     if (!staged) return 0;
@@ -739,6 +742,32 @@ int dispatch(Stager& st, const ArmEntry* a, int dtype, F&& fn, WlHold* held = nu
   if (held) held->release();  // everything that uses the shared scratch is enqueued
   HIPCHK(le);
   return st.finish();
+}
+
+// a kernel's parameter block in both arithmetic types, make(T()) building the T one; of(dtype) is the one a launch reads
+template <class B64, class B32>
+struct Blocks {
+  B64 f64;
+  B32 f32;
+  const void* of(int dtype) const { return dtype == ABRK_F64 ? (const void*)&f64 : (const void*)&f32; }
+};
+template <class Make>
+auto blocks(Make make) -> Blocks<decltype(make(0.0)), decltype(make(0.0f))> {
+  return {make(0.0), make(0.0f)};
+}
+
+// The ABRK_ESINGULAR word of an OSC-law call, stored in both parameter blocks before run() dispatches the call.  Host
+// arrays (st.staged): the calling thread's word, cleared first, and the call returns the code once its outputs are back.
+// Device pointers: the word of their (device, stream), reported by whatever drains that stream next.  `given` (the
+// shards of abrk_osc_generate_sharded): the caller's word, which the caller clears and takes itself.
+template <class OscBlocks, class Run>
+int with_status_word(const Stager& st, OscBlocks& pb, StatusWord* given, Run&& run) {
+  StatusWord* sw = given ? given : status_word(st.staged, st.device, st.stream);
+  const bool own = st.staged && !given;
+  pb.f64.status = pb.f32.status = sw ? sw->dev : nullptr;
+  if (sw && own) *sw->host = 0;  // (this thread's word: nothing of an earlier, failed call is left in it)
+  const int rc = run();
+  return rc == 0 && own && sw && sw->take() ? singular_error() : rc;
 }
 
 // Worklist of the six-row OSC kernels (rows whose law needs the truncating pseudo-inverse are deferred to a second pass,
@@ -1047,16 +1076,11 @@ extern "C" int abrk_dynamics_batch(int arm_id, int dtype, int64_t B, const void*
   if (int rc = use_device(device)) return rc;
   const size_t s = esz(dtype);
   Stager st{device, (hipStream_t)stream};
-  DynArgs da;
-  memset(&da, 0, sizeof da);
-  const void* q_ = st.add(q, B * n * s, true, false);
-  const void* dq_ = (want & (ABRK_WANT_C | ABRK_WANT_DJ)) ? st.add(dq, B * n * s, true, false) : nullptr;
-  void* o_[10];
-  for (int i = 0; i < 10; i++) o_[i] = (want >> i & 1) ? st.add(outs[i], B * per[i] * s, false, true) : nullptr;
+  DynArgs da{};
+  st.in(&da.q, q, B * n * s);
+  st.in(&da.dq, (want & (ABRK_WANT_C | ABRK_WANT_DJ)) ? dq : nullptr, B * n * s);
+  for (int i = 0; i < 10; i++) st.out(&da.out[i], (want >> i & 1) ? outs[i] : nullptr, B * per[i] * s);
   if (int rc = st.reserve()) return rc;
-  da.q = st.fix(q_, q);
-  da.dq = dq_ ? st.fix(dq_, dq) : nullptr;
-  for (int i = 0; i < 10; i++) da.out[i] = (want >> i & 1) ? st.fix(o_[i], outs[i]) : nullptr;
   da.frame = frame;
   da.m = frame_m(frame, n);
   for (int r = 0; r < 3; r++) da.off[r] = x_off ? x_off[r] : 0.0;
@@ -1067,10 +1091,12 @@ extern "C" int abrk_dynamics_batch(int arm_id, int dtype, int64_t B, const void*
 }
 
 // ------------------------------------------------------------------------------- OSC
+// word: the ABRK_ESINGULAR word a sharded call hands its shards (with_status_word); null: the call's own
 static int osc_generate_impl(int arm_id, int dtype, const abrk_osc_params* P, int64_t B, const void* q,
                              const void* dq, const void* target, const void* target_velocity,
                              void* integrated_error, const void* u_null_ext, void* u, void* training_signal,
-                             uint32_t want, const abrk_dyn_out* out, int device, void* stream);
+                             uint32_t want, const abrk_dyn_out* out, int device, void* stream,
+                             StatusWord* word = nullptr);
 
 extern "C" int abrk_osc_generate_batch(int arm_id, int dtype, const abrk_osc_params* P, int64_t B, const void* q,
                                        const void* dq, const void* target, const void* target_velocity,
@@ -1096,7 +1122,7 @@ extern "C" int abrk_osc_generate_full_batch(int arm_id, int dtype, const abrk_os
 static int osc_generate_impl(int arm_id, int dtype, const abrk_osc_params* P, int64_t B, const void* q,
                              const void* dq, const void* target, const void* target_velocity,
                              void* integrated_error, const void* u_null_ext, void* u, void* training_signal,
-                             uint32_t want, const abrk_dyn_out* out, int device, void* stream) {
+                             uint32_t want, const abrk_dyn_out* out, int device, void* stream, StatusWord* word) {
   ArmEntry* a;
   if (int rc = check_common(arm_id, dtype, B, &a)) return rc;
   const int n = a->desc.n_joints;
@@ -1122,56 +1148,40 @@ static int osc_generate_impl(int arm_id, int dtype, const abrk_osc_params* P, in
   if (int rc = use_device(device)) return rc;
   const size_t s = esz(dtype);
   Stager st{device, (hipStream_t)stream};
-  void* ie = (P->ki != 0) ? integrated_error : nullptr;
-  const void* q_ = st.add(q, B * n * s, true, false);
-  const void* dq_ = st.add(dq, B * n * s, true, false);
-  const void* t_ = st.add(target, B * 6 * s, true, false);
-  const void* tv_ = st.add(target_velocity, B * 6 * s, true, false);
-  void* ie_ = st.add(ie, B * 6 * s, true, true);
-  const void* une_ = st.add(u_null_ext, B * n * s, true, false);
-  void* u_ = st.add(u, B * n * s, false, true);
-  void* ts_ = st.add(training_signal, B * n * s, false, true);
-  const size_t per[6] = {3, (size_t)6 * n, (size_t)n * n, (size_t)n, (size_t)n * n, (size_t)6 * n};
-  void* o_[6];
-  for (int i = 0; i < 6; i++) o_[i] = (want >> i & 1) ? st.add(wout[i], B * per[i] * s, false, true) : nullptr;
-  if (int rc = st.reserve()) return rc;
   OscArgs oa;
+  st.in(&oa.q, q, B * n * s);
+  st.in(&oa.dq, dq, B * n * s);
+  st.in(&oa.target, target, B * 6 * s);
+  st.in(&oa.tv, target_velocity, B * 6 * s);
+  st.inout(&oa.ierr, P->ki != 0 ? integrated_error : nullptr, B * 6 * s);
+  st.in(&oa.une, u_null_ext, B * n * s);
+  st.out(&oa.u, u, B * n * s);
+  st.out(&oa.ts, training_signal, B * n * s);
+  const size_t per[6] = {3, (size_t)6 * n, (size_t)n * n, (size_t)n, (size_t)n * n, (size_t)6 * n};
+  for (int i = 0; i < 6; i++) st.out(&oa.out[i], (want >> i & 1) ? wout[i] : nullptr, B * per[i] * s);
+  if (int rc = st.reserve()) return rc;
   oa.want = want;
-  for (int i = 0; i < 6; i++) oa.out[i] = (want >> i & 1) ? st.fix(o_[i], wout[i]) : nullptr;
-  oa.q = st.fix(q_, q);
-  oa.dq = st.fix(dq_, dq);
-  oa.target = st.fix(t_, target);
-  oa.tv = st.fix(tv_, target_velocity);
-  oa.ierr = st.fix(ie_, ie);
-  oa.une = st.fix(une_, u_null_ext);
-  oa.u = st.fix(u_, u);
-  oa.ts = st.fix(ts_, training_signal);
   oa.use_C = P->use_C ? 1 : 0;
   oa.fast = osc_fast_rows(*P, n, u_null_ext != nullptr);
   WlHold wl_hold;  // the (device, stream) worklist stays ours until the launches are enqueued
   if (oa.fast == 0 && !want)
     if (int rc = worklist_for(device, (hipStream_t)stream, B, n, dtype, &oa.wl, &oa.rec, wl_hold)) return rc;
-  OscP<double> p64 = make_oscp<double>(*P, n);
-  OscP<float> p32 = make_oscp<float>(*P, n);
-  StatusWord* sw = status_word(st.staged, device, stream);
-  p64.status = p32.status = sw ? sw->dev : nullptr;
-  if (sw && st.staged) *sw->host = 0;  // (this thread's word: nothing of an earlier, failed call is left in it)
+  auto pb = blocks([&](auto t) { return make_oscp<decltype(t)>(*P, n); });
   const ArmOps* ops = a->ops;
   const hipStream_t hs = (hipStream_t)stream;
   // hand-over mode: the arm's first pass, then the arm-independent finish kernel on the records it left
   FinishArgs fa{oa.wl, oa.rec, (P->n_null > 0 || u_null_ext) ? 1 : 0, finish_slots_for(B), finish_rounds_for(B),
                 oa.u, oa.ts, finish_group_for(B)};
-  const int rc = dispatch(st, a, dtype, [=](const void* rt) {
-    OscArgs o = oa;
-    o.P = dtype == ABRK_F64 ? (const void*)&p64 : (const void*)&p32;
-    const LaunchArgs la{rt, (long)B, hs};
-    const hipError_t e = ops->osc(dtype, la, o);
-    if (e != hipSuccess || !o.rec) return e;
-    return launch_osc6_finish(n, dtype, la, fa);
-  }, &wl_hold);
-  // host arrays: the call is complete (outputs copied back) - report a non-positive-definite M now
-  if (rc == 0 && st.staged && sw && sw->take()) return singular_error();
-  return rc;
+  return with_status_word(st, pb, word, [&] {
+    return dispatch(st, a, dtype, [=](const void* rt) {
+      OscArgs o = oa;
+      o.P = pb.of(dtype);
+      const LaunchArgs la{rt, (long)B, hs};
+      const hipError_t e = ops->osc(dtype, la, o);
+      if (e != hipSuccess || !o.rec) return e;
+      return launch_osc6_finish(n, dtype, la, fa);
+    }, &wl_hold);
+  });
 }
 
 // ------------------------------------------------------------------------------- OSC, wave-cooperative mapping
@@ -1198,20 +1208,15 @@ extern "C" int abrk_osc_generate_coop_batch(int arm_id, int dtype, const abrk_os
   if (int rc = use_device(device)) return rc;
   const size_t s = esz(dtype);
   Stager st{device, (hipStream_t)stream};
-  const void* q_ = st.add(q, B * n * s, true, false);
-  const void* dq_ = st.add(dq, B * n * s, true, false);
-  const void* t_ = st.add(target, B * 6 * s, true, false);
-  void* u_ = st.add(u, B * n * s, false, true);
-  void* ts_ = st.add(training_signal, B * n * s, false, true);
-  if (int rc = st.reserve()) return rc;
   CoopArgs ca;
   ca.P = nullptr;
   ca.lanes = lanes_per_arm;
-  ca.q = st.fix(q_, q);
-  ca.dq = st.fix(dq_, dq);
-  ca.target = st.fix(t_, target);
-  ca.u = st.fix(u_, u);
-  ca.ts = st.fix(ts_, training_signal);
+  st.in(&ca.q, q, B * n * s);
+  st.in(&ca.dq, dq, B * n * s);
+  st.in(&ca.target, target, B * 6 * s);
+  st.out(&ca.u, u, B * n * s);
+  st.out(&ca.ts, training_signal, B * n * s);
+  if (int rc = st.reserve()) return rc;
   const OscP<double> p64 = make_oscp<double>(*P, n);
   const hipStream_t hs = (hipStream_t)stream;
   return dispatch(st, a, dtype, [=](const void*) {
@@ -1278,9 +1283,12 @@ ShardCtx* shard_ctx(int device, int slot, size_t need) {
 namespace {
 // One host batch over several devices: [0, B) is cut into n_shards contiguous row ranges (sizes differing by at most one
 // row - abr_control_amd/sharding.py shard_range), the pieces of shard g are staged to devices[g] on a stream of its own,
-// `launch(dev, rows, stream)` enqueues the kernel(s) on it (dev[k]: device address of piece k, null for an absent one),
-// and only when every shard of a device is in flight are that device's results collected.  No collective: rows are
-// independent.
+// `launch(dev, rows, device, stream)` enqueues the shard through the single-device entry point (dev[k]: device address
+// of piece k, null for an absent one; -> an ABRK_* code), and only when every shard of a device is in flight are that
+// device's results collected.  No collective: rows are independent.
+// Lock order: g_shard_dev_mu[device] is held while a shard's launch takes the six-row law's worklist slot mutex of its
+// (device, stream) (worklist_for); the *_resident calls take slot mutexes without a device lock, and nothing takes a
+// device lock while holding a slot mutex - keep it one-way.
 struct ShardPiece {
   const void* host_in;
   void* host_out;
@@ -1359,7 +1367,7 @@ int run_sharded(int64_t B, int n_shards, const int* devices, const ShardPiece* p
           HIPCHK(hipMemcpyAsync(sh.dev[k], (const char*)pc.host_in + sh.r0 * pc.per_row, sh.rows * pc.per_row,
                                 hipMemcpyHostToDevice, sh.c->stream));
       }
-      HIPCHK(launch(sh.dev, sh.rows, sh.c->stream));
+      if (int rc = launch(sh.dev, sh.rows, device, sh.c->stream)) return rc;
     }
     // every kernel of this device is enqueued; now collect (a device-to-host copy into pageable memory waits for its shard)
     for (Shard& sh : shards) {
@@ -1405,34 +1413,19 @@ extern "C" int abrk_osc_generate_sharded(int arm_id, int dtype, const abrk_osc_p
   if (int rc = osc_generate_impl(arm_id, dtype, P, 0, q, dq, target, target_velocity, integrated_error, u_null_ext, u,
                                  training_signal, 0, nullptr, devices[0], nullptr))
     return rc;
-  ArmEntry* a = get_arm(arm_id);
-  const int n = a->desc.n_joints;
+  const int n = get_arm(arm_id)->desc.n_joints;
   const size_t s = esz(dtype);
   void* ie = (P->ki != 0) ? integrated_error : nullptr;
-  OscP<double> p64 = make_oscp<double>(*P, n);
-  OscP<float> p32 = make_oscp<float>(*P, n);
-  // (a synchronous call: the calling thread's word, shared by every shard - the word is portable pinned host memory)
-  StatusWord* sw = status_word(true, devices[0]);
-  p64.status = p32.status = sw ? sw->dev : nullptr;
+  // a synchronous call: the calling thread's word, shared by every shard (portable pinned host memory), reports this
+  // batch alone - the words of the shard streams (left there by *_resident calls) are neither cleared nor taken
+  StatusWord none, *sw = status_word(true, devices[0]);
   if (sw) *sw->host = 0;
   const ShardPiece pieces[8] = {{q, nullptr, n * s},           {dq, nullptr, n * s},        {target, nullptr, 6 * s},
                                 {target_velocity, nullptr, 6 * s}, {ie, ie, 6 * s},          {u_null_ext, nullptr, n * s},
                                 {nullptr, u, n * s},           {nullptr, training_signal, n * s}};
-  const int use_C = P->use_C ? 1 : 0, fast = osc_fast_rows(*P, n, u_null_ext != nullptr);
-  const int rc = run_sharded(B, n_shards, devices, pieces, 8, [&](char* const* dev, int64_t rows, hipStream_t st) {
-    OscArgs oa;
-    oa.q = dev[0];
-    oa.dq = dev[1];
-    oa.target = dev[2];
-    oa.tv = dev[3];
-    oa.ierr = dev[4];
-    oa.une = dev[5];
-    oa.u = dev[6];
-    oa.ts = dev[7];
-    oa.use_C = use_C;
-    oa.fast = fast;
-    oa.P = dtype == ABRK_F64 ? (const void*)&p64 : (const void*)&p32;
-    return a->ops->osc(dtype, LaunchArgs{arm_table(a, dtype), (long)rows, st}, oa);
+  const int rc = run_sharded(B, n_shards, devices, pieces, 8, [&](char* const* dev, int64_t rows, int device, hipStream_t st) {
+    return osc_generate_impl(arm_id, dtype, P, rows, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6], dev[7], 0,
+                             nullptr, device, st, sw ? sw : &none);
   });
   if (rc == 0 && sw && sw->take()) return singular_error();
   return rc;
@@ -1446,25 +1439,14 @@ extern "C" int abrk_sliding_generate_sharded(int arm_id, int dtype, const abrk_s
   if (int rc = abrk_sliding_generate_batch(arm_id, dtype, P, 0, q, dq, target, target_velocity, target_acc, u, s_out,
                                            devices[0], nullptr))
     return rc;
-  ArmEntry* a = get_arm(arm_id);
-  const int n = a->desc.n_joints, nt = P->cartesian ? 3 : n;
+  const int n = get_arm(arm_id)->desc.n_joints, nt = P->cartesian ? 3 : n;
   const size_t s = esz(dtype);
-  const SlidingP<double> p64 = make_slidingp<double>(*P, n);
-  const SlidingP<float> p32 = make_slidingp<float>(*P, n);
   const ShardPiece pieces[7] = {{q, nullptr, n * s},  {dq, nullptr, n * s},         {target, nullptr, nt * s},
                                 {target_velocity, nullptr, nt * s}, {target_acc, nullptr, nt * s},
                                 {nullptr, u, n * s},  {nullptr, s_out, n * s}};
-  return run_sharded(B, n_shards, devices, pieces, 7, [&](char* const* dev, int64_t rows, hipStream_t st) {
-    SlidingArgs sa;
-    sa.q = dev[0];
-    sa.dq = dev[1];
-    sa.target = dev[2];
-    sa.tv = dev[3];
-    sa.ta = dev[4];
-    sa.u = dev[5];
-    sa.s = dev[6];
-    sa.P = dtype == ABRK_F64 ? (const void*)&p64 : (const void*)&p32;
-    return a->ops->sliding(dtype, LaunchArgs{arm_table(a, dtype), (long)rows, st}, sa);
+  return run_sharded(B, n_shards, devices, pieces, 7, [&](char* const* dev, int64_t rows, int device, hipStream_t st) {
+    return abrk_sliding_generate_batch(arm_id, dtype, P, rows, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6],
+                                       device, st);
   });
 }
 
@@ -1475,22 +1457,13 @@ extern "C" int abrk_joint_generate_sharded(int arm_id, int dtype, const abrk_nul
   if (int rc = abrk_joint_generate_batch(arm_id, dtype, ctrl, account_for_gravity, 0, q, dq, target, target_velocity, u,
                                          devices[0], nullptr))
     return rc;
-  ArmEntry* a = get_arm(arm_id);
-  const int n = a->desc.n_joints;
+  const int n = get_arm(arm_id)->desc.n_joints;
   const size_t s = esz(dtype);
-  const JointP<double> p64 = make_jointp<double>(*ctrl, account_for_gravity);
-  const JointP<float> p32 = make_jointp<float>(*ctrl, account_for_gravity);
   const ShardPiece pieces[5] = {{q, nullptr, n * s}, {dq, nullptr, n * s}, {target, nullptr, n * s},
                                 {target_velocity, nullptr, n * s}, {nullptr, u, n * s}};
-  return run_sharded(B, n_shards, devices, pieces, 5, [&](char* const* dev, int64_t rows, hipStream_t st) {
-    JointArgs ja;
-    ja.q = dev[0];
-    ja.dq = dev[1];
-    ja.target = dev[2];
-    ja.tv = dev[3];
-    ja.u = dev[4];
-    ja.P = dtype == ABRK_F64 ? (const void*)&p64 : (const void*)&p32;
-    return a->ops->joint(dtype, LaunchArgs{arm_table(a, dtype), (long)rows, st}, ja);
+  return run_sharded(B, n_shards, devices, pieces, 5, [&](char* const* dev, int64_t rows, int device, hipStream_t st) {
+    return abrk_joint_generate_batch(arm_id, dtype, ctrl, account_for_gravity, rows, dev[0], dev[1], dev[2], dev[3],
+                                     dev[4], device, st);
   });
 }
 
@@ -1499,26 +1472,16 @@ extern "C" int abrk_dynamics_sharded(int arm_id, int dtype, int64_t B, const voi
                                      const int* devices) {
   if (n_shards < 1 || !devices) return fail(ABRK_EINVAL, "n_shards must be >= 1 and devices non-NULL");
   if (int rc = abrk_dynamics_batch(arm_id, dtype, 0, q, dq, frame, x_off, want, out, devices[0], nullptr)) return rc;
-  ArmEntry* a = get_arm(arm_id);
-  const int n = a->desc.n_joints;
+  const int n = get_arm(arm_id)->desc.n_joints;
   const size_t s = esz(dtype);
   void* const* outs = reinterpret_cast<void* const*>(out);
   const size_t per[10] = {3, (size_t)6 * n, (size_t)n * n, (size_t)n, (size_t)n * n, (size_t)6 * n, 9, 16, 16, 4};
   const bool vel = (want & (ABRK_WANT_C | ABRK_WANT_DJ)) != 0;
   ShardPiece pieces[12] = {{q, nullptr, n * s}, {vel ? dq : nullptr, nullptr, n * s}};
   for (int i = 0; i < 10; i++) pieces[2 + i] = {nullptr, (want >> i & 1) ? outs[i] : nullptr, per[i] * s};
-  DynArgs da0;
-  memset(&da0, 0, sizeof da0);
-  da0.frame = frame;
-  da0.m = frame_m(frame, n);
-  for (int r = 0; r < 3; r++) da0.off[r] = x_off ? x_off[r] : 0.0;
-  da0.want = want;
-  return run_sharded(B, n_shards, devices, pieces, 12, [&](char* const* dev, int64_t rows, hipStream_t st) {
-    DynArgs da = da0;
-    da.q = dev[0];
-    da.dq = dev[1];
-    for (int i = 0; i < 10; i++) da.out[i] = dev[2 + i];
-    return a->ops->dyn(dtype, LaunchArgs{arm_table(a, dtype), (long)rows, st}, da);
+  return run_sharded(B, n_shards, devices, pieces, 12, [&](char* const* dev, int64_t rows, int device, hipStream_t st) {
+    const abrk_dyn_out o = {dev[2], dev[3], dev[4], dev[5], dev[6], dev[7], dev[8], dev[9], dev[10], dev[11]};
+    return abrk_dynamics_batch(arm_id, dtype, rows, dev[0], dev[1], frame, x_off, want, &o, device, st);
   });
 }
 
@@ -1706,29 +1669,21 @@ extern "C" int abrk_sliding_generate_batch(int arm_id, int dtype, const abrk_sli
   const size_t s = esz(dtype);
   const int nt = P->cartesian ? 3 : n;
   Stager st{device, (hipStream_t)stream};
-  const void* q_ = st.add(q, B * n * s, true, false);
-  const void* dq_ = st.add(dq, B * n * s, true, false);
-  const void* t_ = st.add(target, B * nt * s, true, false);
-  const void* tv_ = st.add(target_velocity, B * nt * s, true, false);
-  const void* ta_ = st.add(target_acc, B * nt * s, true, false);
-  void* u_ = st.add(u, B * n * s, false, true);
-  void* s_ = st.add(s_out, B * n * s, false, true);
-  if (int rc = st.reserve()) return rc;
   SlidingArgs sa;
-  sa.q = st.fix(q_, q);
-  sa.dq = st.fix(dq_, dq);
-  sa.target = st.fix(t_, target);
-  sa.tv = st.fix(tv_, target_velocity);
-  sa.ta = st.fix(ta_, target_acc);
-  sa.u = st.fix(u_, u);
-  sa.s = st.fix(s_, s_out);
-  const SlidingP<double> p64 = make_slidingp<double>(*P, n);
-  const SlidingP<float> p32 = make_slidingp<float>(*P, n);
+  st.in(&sa.q, q, B * n * s);
+  st.in(&sa.dq, dq, B * n * s);
+  st.in(&sa.target, target, B * nt * s);
+  st.in(&sa.tv, target_velocity, B * nt * s);
+  st.in(&sa.ta, target_acc, B * nt * s);
+  st.out(&sa.u, u, B * n * s);
+  st.out(&sa.s, s_out, B * n * s);
+  if (int rc = st.reserve()) return rc;
+  const auto pb = blocks([&](auto t) { return make_slidingp<decltype(t)>(*P, n); });
   const ArmOps* ops = a->ops;
   const hipStream_t hs = (hipStream_t)stream;
   return dispatch(st, a, dtype, [=](const void* rt) {
     SlidingArgs o = sa;
-    o.P = dtype == ABRK_F64 ? (const void*)&p64 : (const void*)&p32;
+    o.P = pb.of(dtype);
     return ops->sliding(dtype, LaunchArgs{rt, (long)B, hs}, o);
   });
 }
@@ -1748,25 +1703,19 @@ extern "C" int abrk_joint_generate_batch(int arm_id, int dtype, const abrk_null_
   if (int rc = use_device(device)) return rc;
   const size_t s = esz(dtype);
   Stager st{device, (hipStream_t)stream};
-  const void* q_ = st.add(q, B * n * s, true, false);
-  const void* dq_ = st.add(dq, B * n * s, true, false);
-  const void* t_ = st.add(target, B * n * s, true, false);
-  const void* tv_ = st.add(target_velocity, B * n * s, true, false);
-  void* u_ = st.add(u, B * n * s, false, true);
-  if (int rc = st.reserve()) return rc;
   JointArgs ja;
-  ja.q = st.fix(q_, q);
-  ja.dq = st.fix(dq_, dq);
-  ja.target = st.fix(t_, target);
-  ja.tv = st.fix(tv_, target_velocity);
-  ja.u = st.fix(u_, u);
-  const JointP<double> p64 = make_jointp<double>(*ctrl, account_for_gravity);
-  const JointP<float> p32 = make_jointp<float>(*ctrl, account_for_gravity);
+  st.in(&ja.q, q, B * n * s);
+  st.in(&ja.dq, dq, B * n * s);
+  st.in(&ja.target, target, B * n * s);
+  st.in(&ja.tv, target_velocity, B * n * s);
+  st.out(&ja.u, u, B * n * s);
+  if (int rc = st.reserve()) return rc;
+  const auto pb = blocks([&](auto t) { return make_jointp<decltype(t)>(*ctrl, account_for_gravity); });
   const ArmOps* ops = a->ops;
   const hipStream_t hs = (hipStream_t)stream;
   return dispatch(st, a, dtype, [=](const void* rt) {
     JointArgs o = ja;
-    o.P = dtype == ABRK_F64 ? (const void*)&p64 : (const void*)&p32;
+    o.P = pb.of(dtype);
     return ops->joint(dtype, LaunchArgs{rt, (long)B, hs}, o);
   });
 }
@@ -1785,17 +1734,15 @@ extern "C" int abrk_avoid_joint_limits_generate_batch(int n_joints, int dtype, c
   const int n = n_joints;
   const size_t s = esz(dtype);
   Stager st{device, (hipStream_t)stream};
-  const void* q_ = st.add(q, B * n * s, true, false);
-  void* u_ = st.add(u, B * n * s, accumulate != 0, true);
+  const void* qd;
+  void* ud;
+  st.in(&qd, q, B * n * s);
+  st.bind(&ud, u, B * n * s, accumulate != 0, true);
   if (int rc = st.reserve()) return rc;
-  const LimitsP<double> p64 = make_limitsp<double>(*params);
-  const LimitsP<float> p32 = make_limitsp<float>(*params);
-  const void* qd = st.fix(q_, q);
-  void* ud = st.fix(u_, u);
+  const auto pb = blocks([&](auto t) { return make_limitsp<decltype(t)>(*params); });
   const hipStream_t hs = (hipStream_t)stream;
   return dispatch(st, nullptr, dtype, [=](const void*) {
-    return launch_limits(n, dtype, LaunchArgs{nullptr, (long)B, hs},
-                         dtype == ABRK_F64 ? (const void*)&p64 : (const void*)&p32, qd, ud, accumulate != 0);
+    return launch_limits(n, dtype, LaunchArgs{nullptr, (long)B, hs}, pb.of(dtype), qd, ud, accumulate != 0);
   });
 }
 
@@ -1811,17 +1758,14 @@ extern "C" int abrk_floating_generate_batch(int arm_id, int dtype, int dynamic, 
   if (int rc = use_device(device)) return rc;
   const size_t s = esz(dtype);
   Stager st{device, (hipStream_t)stream};
-  const void* q_ = st.add(q, B * n * s, true, false);
-  const void* dq_ = dynamic ? st.add(dq, B * n * s, true, false) : nullptr;
-  void* u_ = st.add(u, B * n * s, accumulate != 0, true);
-  if (int rc = st.reserve()) return rc;
   FloatingArgs fa;
   fa.dynamic = dynamic != 0;
   fa.task_space = task_space != 0;
   fa.acc = accumulate != 0;
-  fa.q = st.fix(q_, q);
-  fa.dq = dynamic ? st.fix(dq_, dq) : nullptr;
-  fa.u = st.fix(u_, u);
+  st.in(&fa.q, q, B * n * s);
+  st.in(&fa.dq, dynamic ? dq : nullptr, B * n * s);
+  st.bind(&fa.u, u, B * n * s, accumulate != 0, true);
+  if (int rc = st.reserve()) return rc;
   const ArmOps* ops = a->ops;
   const hipStream_t hs = (hipStream_t)stream;
   return dispatch(st, a, dtype, [=](const void* rt) { return ops->floating(dtype, LaunchArgs{rt, (long)B, hs}, fa); });
@@ -1842,21 +1786,17 @@ extern "C" int abrk_avoid_obstacles_generate_batch(int arm_id, int dtype, const 
   if (int rc = use_device(device)) return rc;
   const size_t s = esz(dtype);
   Stager st{device, (hipStream_t)stream};
-  const void* q_ = st.add(q, B * n * s, true, false);
-  void* u_ = st.add(u, B * n * s, accumulate != 0, true);
-  if (int rc = st.reserve()) return rc;
-  ObstaclesArgs oa;
-  const ObsP<double> p64 = make_obsp<double>(*params);
-  const ObsP<float> p32 = make_obsp<float>(*params);
-  oa.P = nullptr;
+  ObstaclesArgs oa{};
   oa.acc = accumulate != 0;
-  oa.q = st.fix(q_, q);
-  oa.u = st.fix(u_, u);
+  st.in(&oa.q, q, B * n * s);
+  st.bind(&oa.u, u, B * n * s, accumulate != 0, true);
+  if (int rc = st.reserve()) return rc;
+  const auto pb = blocks([&](auto t) { return make_obsp<decltype(t)>(*params); });
   const ArmOps* ops = a->ops;
   const hipStream_t hs = (hipStream_t)stream;
   return dispatch(st, a, dtype, [=](const void* rt) {
     ObstaclesArgs o = oa;
-    o.P = dtype == ABRK_F64 ? (const void*)&p64 : (const void*)&p32;
+    o.P = pb.of(dtype);
     return ops->obstacles(dtype, LaunchArgs{rt, (long)B, hs}, o);
   });
 }
@@ -1893,53 +1833,31 @@ extern "C" int abrk_osc_law_batch(int n_joints, int dtype, const abrk_osc_params
   if (int rc = use_device(device)) return rc;
   const size_t s = esz(dtype);
   Stager st{device, (hipStream_t)stream};
-  void* ie = (P->ki != 0) ? integrated_error : nullptr;
-  const void* c_in = P->use_C ? Cdq : nullptr;
-  const void* g_in = P->use_g ? g : nullptr;
-  const void* J_ = st.add(J, B * 6 * n * s, true, false);
-  const void* M_ = st.add(M, B * n * n * s, true, false);
-  const void* g_ = st.add(g_in, B * n * s, true, false);
-  const void* c_ = st.add(c_in, B * n * s, true, false);
-  const void* x_ = st.add(xyz, B * 3 * s, true, false);
-  const void* R_ = st.add(R, B * 9 * s, true, false);
-  const void* q_ = st.add(q, B * n * s, true, false);
-  const void* dq_ = st.add(dq, B * n * s, true, false);
-  const void* t_ = st.add(target, B * 6 * s, true, false);
-  const void* tv_ = st.add(target_velocity, B * 6 * s, true, false);
-  void* ie_ = st.add(ie, B * 6 * s, true, true);
-  const void* une_ = st.add(u_null_ext, B * n * s, true, false);
-  void* u_ = st.add(u, B * n * s, false, true);
-  void* ts_ = st.add(training_signal, B * n * s, false, true);
+  LawArgs a{};
+  st.in(&a.J, J, B * 6 * n * s);
+  st.in(&a.M, M, B * n * n * s);
+  st.in(&a.g, P->use_g ? g : nullptr, B * n * s);
+  st.in(&a.c, P->use_C ? Cdq : nullptr, B * n * s);
+  st.in(&a.xyz, xyz, B * 3 * s);
+  st.in(&a.R, R, B * 9 * s);
+  st.in(&a.q, q, B * n * s);
+  st.in(&a.dq, dq, B * n * s);
+  st.in(&a.target, target, B * 6 * s);
+  st.in(&a.tv, target_velocity, B * 6 * s);
+  st.inout(&a.ierr, P->ki != 0 ? integrated_error : nullptr, B * 6 * s);
+  st.in(&a.une, u_null_ext, B * n * s);
+  st.out(&a.u, u, B * n * s);
+  st.out(&a.ts, training_signal, B * n * s);
   if (int rc = st.reserve()) return rc;
-  LawArgs a;
-  a.J = st.fix(J_, J);
-  a.M = st.fix(M_, M);
-  a.g = st.fix(g_, g_in);
-  a.c = st.fix(c_, c_in);
-  a.xyz = st.fix(x_, xyz);
-  a.R = st.fix(R_, R);
-  a.q = st.fix(q_, q);
-  a.dq = st.fix(dq_, dq);
-  a.target = st.fix(t_, target);
-  a.tv = st.fix(tv_, target_velocity);
-  a.ierr = st.fix(ie_, ie);
-  a.une = st.fix(une_, u_null_ext);
-  a.u = st.fix(u_, u);
-  a.ts = st.fix(ts_, training_signal);
-  OscP<double> p64 = make_oscp<double>(*P, n);
-  OscP<float> p32 = make_oscp<float>(*P, n);
-  StatusWord* sw = status_word(st.staged, device, stream);
-  p64.status = p32.status = sw ? sw->dev : nullptr;
-  if (sw && st.staged) *sw->host = 0;  // (this thread's word: nothing of an earlier, failed call is left in it)
-  a.P = nullptr;
+  auto pb = blocks([&](auto t) { return make_oscp<decltype(t)>(*P, n); });
   const hipStream_t hs = (hipStream_t)stream;
-  const int rc = dispatch(st, nullptr, dtype, [=](const void*) {
-    LawArgs o = a;
-    o.P = dtype == ABRK_F64 ? (const void*)&p64 : (const void*)&p32;
-    return launch_osc_law(n, dtype, LaunchArgs{nullptr, (long)B, hs}, o);
+  return with_status_word(st, pb, nullptr, [&] {
+    return dispatch(st, nullptr, dtype, [=](const void*) {
+      LawArgs o = a;
+      o.P = pb.of(dtype);
+      return launch_osc_law(n, dtype, LaunchArgs{nullptr, (long)B, hs}, o);
+    });
   });
-  if (rc == 0 && st.staged && sw && sw->take()) return singular_error();
-  return rc;
 }
 
 // ------------------------------------------------------------------------------- helper methods of OSC
@@ -1962,13 +1880,15 @@ extern "C" int abrk_osc_mx_batch(int n_joints, int k, int dtype, int64_t B, cons
   if (int rc = use_device(device)) return rc;
   const size_t s = esz(dtype);
   Stager st{device, (hipStream_t)stream};
-  const void* M_ = st.add(M, B * n * n * s, true, false);
-  const void* J_ = st.add(J, B * k * n * s, true, false);
-  void* X_ = st.add(Mx, B * k * k * s, false, true);
-  void* I_ = st.add(M_inv, B * n * n * s, false, true);
+  const void *Md, *Jd;
+  void *Xd, *Id;
+  st.in(&Md, M, B * n * n * s);
+  st.in(&Jd, J, B * k * n * s);
+  st.out(&Xd, Mx, B * k * k * s);
+  st.out(&Id, M_inv, B * n * n * s);
   if (int rc = st.reserve()) return rc;
   LaunchArgs la{nullptr, (long)B, (hipStream_t)stream};
-  HIPCHK(launch_osc_mx(n, dtype, la, k, threshold, st.fix(M_, M), st.fix(J_, J), st.fix(X_, Mx), st.fix(I_, M_inv)));
+  HIPCHK(launch_osc_mx(n, dtype, la, k, threshold, Md, Jd, Xd, Id));
   return st.finish();
 }
 
@@ -1982,12 +1902,14 @@ extern "C" int abrk_osc_velocity_limiting_batch(int dtype, const abrk_osc_params
   if (int rc = use_device(device)) return rc;
   const size_t s = esz(dtype);
   Stager st{device, (hipStream_t)stream};
-  const void* i_ = st.add(u_task, B * 6 * s, true, false);
-  void* o_ = st.add(out, B * 6 * s, false, true);
+  const void* id;
+  void* od;
+  st.in(&id, u_task, B * 6 * s);
+  st.out(&od, out, B * 6 * s);
   if (int rc = st.reserve()) return rc;
   LaunchArgs la{nullptr, (long)B, (hipStream_t)stream};
   const double g[5] = {P->kp, P->ko, P->kv, P->vmax[0], P->vmax[1]};
-  HIPCHK(launch_velocity_limiting(dtype, la, g, st.fix(i_, u_task), st.fix(o_, out)));
+  HIPCHK(launch_velocity_limiting(dtype, la, g, id, od));
   return st.finish();
 }
 
@@ -2002,13 +1924,14 @@ extern "C" int abrk_osc_orientation_forces_batch(int algorithm, int dtype, int64
   if (int rc = use_device(device)) return rc;
   const size_t s = esz(dtype);
   Stager st{device, (hipStream_t)stream};
-  const void* R_ = st.add(R, B * 9 * s, true, false);
-  const void* a_ = st.add(target_abg, B * 3 * s, true, false);
-  void* o_ = st.add(u_task_orientation, B * 3 * s, false, true);
+  const void *Rd, *ad;
+  void* od;
+  st.in(&Rd, R, B * 9 * s);
+  st.in(&ad, target_abg, B * 3 * s);
+  st.out(&od, u_task_orientation, B * 3 * s);
   if (int rc = st.reserve()) return rc;
   LaunchArgs la{nullptr, (long)B, (hipStream_t)stream};
-  HIPCHK(launch_orientation_forces(dtype, la, algorithm, st.fix(R_, R), st.fix(a_, target_abg),
-                                   st.fix(o_, u_task_orientation)));
+  HIPCHK(launch_orientation_forces(dtype, la, algorithm, Rd, ad, od));
   return st.finish();
 }
 
@@ -2023,13 +1946,14 @@ extern "C" int abrk_transformations_batch(int op, int dtype, int64_t B, const vo
   if (int rc = use_device(device)) return rc;
   const size_t s = esz(dtype);
   Stager st{device, (hipStream_t)stream};
-  const void* b_in = kIn2[op] ? b : nullptr;
-  const void* a_ = st.add(a, B * kIn[op] * s, true, false);
-  const void* b_ = st.add(b_in, B * kIn2[op] * s, true, false);
-  void* o_ = st.add(out, B * kOut[op] * s, false, true);
+  const void *ad, *bd;
+  void* od;
+  st.in(&ad, a, B * kIn[op] * s);
+  st.in(&bd, kIn2[op] ? b : nullptr, B * kIn2[op] * s);
+  st.out(&od, out, B * kOut[op] * s);
   if (int rc = st.reserve()) return rc;
   LaunchArgs la{nullptr, (long)B, (hipStream_t)stream};
-  HIPCHK(launch_transformations(dtype, la, op, st.fix(a_, a), st.fix(b_, b_in), st.fix(o_, out)));
+  HIPCHK(launch_transformations(dtype, la, op, ad, bd, od));
   return st.finish();
 }
 
@@ -2056,18 +1980,16 @@ extern "C" int abrk_twolink_step_batch(int dtype, const abrk_twolink_plant* plan
   if (int rc = use_device(device)) return rc;
   const size_t s = esz(dtype);
   Stager st{device, (hipStream_t)stream};
-  void* q_ = st.add(q, B * 2 * s, true, true);
-  void* dq_ = st.add(dq, B * 2 * s, true, true);
-  const void* u_ = st.add(u, B * 2 * s, true, false);
+  void *qd, *dqd;
+  const void* ud;
+  st.inout(&qd, q, B * 2 * s);
+  st.inout(&dqd, dq, B * 2 * s);
+  st.in(&ud, u, B * 2 * s);
   if (int rc = st.reserve()) return rc;
-  const TwoLinkP<double> k64 = make_plant<double>(*plant);
-  const TwoLinkP<float> k32 = make_plant<float>(*plant);
-  void *qd = st.fix(q_, q), *dqd = st.fix(dq_, dq);
-  const void* ud = st.fix(u_, u);
+  const auto kb = blocks([&](auto t) { return make_plant<decltype(t)>(*plant); });
   const hipStream_t hs = (hipStream_t)stream;
   return dispatch(st, nullptr, dtype, [=](const void*) {
-    return launch_twolink_step(dtype, LaunchArgs{nullptr, (long)B, hs},
-                               dtype == ABRK_F64 ? (const void*)&k64 : (const void*)&k32, qd, dqd, ud);
+    return launch_twolink_step(dtype, LaunchArgs{nullptr, (long)B, hs}, kb.of(dtype), qd, dqd, ud);
   });
 }
 
@@ -2097,45 +2019,31 @@ extern "C" int abrk_osc_rollout_twolink_batch(int arm_id, int dtype, const abrk_
   const size_t s = esz(dtype);
   const size_t n_chk = every > 0 ? (size_t)(n_steps / every) : 0;
   Stager st{device, (hipStream_t)stream};
-  void* ie = (P->ki != 0) ? integrated_error : nullptr;
-  void* q_ = st.add(q, B * 2 * s, true, true);
-  void* dq_ = st.add(dq, B * 2 * s, true, true);
-  const void* t_ = st.add(target, B * 6 * s, true, false);
-  void* ie_ = st.add(ie, B * 6 * s, true, true);
-  void* qt_ = st.add(q_traj, B * n_chk * 2 * s, false, true);
-  void* dqt_ = st.add(dq_traj, B * n_chk * 2 * s, false, true);
-  void* ut_ = st.add(u_traj, B * n_chk * 2 * s, false, true);
+  RolloutArgs ra{};
+  st.inout(&ra.q, q, B * 2 * s);
+  st.inout(&ra.dq, dq, B * 2 * s);
+  st.in(&ra.target, target, B * 6 * s);
+  st.inout(&ra.ierr, P->ki != 0 ? integrated_error : nullptr, B * 6 * s);
+  st.out(&ra.qt, q_traj, B * n_chk * 2 * s);
+  st.out(&ra.dqt, dq_traj, B * n_chk * 2 * s);
+  st.out(&ra.ut, u_traj, B * n_chk * 2 * s);
   if (int rc = st.reserve()) return rc;
-  RolloutArgs ra;
   ra.use_C = P->use_C ? 1 : 0;
   ra.fast = osc_fast_rows(*P, n, false);
   ra.n_steps = n_steps;
   ra.every = every;
-  ra.q = st.fix(q_, q);
-  ra.dq = st.fix(dq_, dq);
-  ra.target = st.fix(t_, target);
-  ra.ierr = st.fix(ie_, ie);
-  ra.qt = st.fix(qt_, q_traj);
-  ra.dqt = st.fix(dqt_, dq_traj);
-  ra.ut = st.fix(ut_, u_traj);
-  OscP<double> p64 = make_oscp<double>(*P, n);
-  OscP<float> p32 = make_oscp<float>(*P, n);
-  StatusWord* sw = status_word(st.staged, device, stream);
-  p64.status = p32.status = sw ? sw->dev : nullptr;
-  if (sw && st.staged) *sw->host = 0;  // (this thread's word: nothing of an earlier, failed call is left in it)
-  const TwoLinkP<double> k64 = make_plant<double>(*plant);
-  const TwoLinkP<float> k32 = make_plant<float>(*plant);
-  ra.P = ra.K = nullptr;
+  auto pb = blocks([&](auto t) { return make_oscp<decltype(t)>(*P, n); });
+  const auto kb = blocks([&](auto t) { return make_plant<decltype(t)>(*plant); });
   const ArmOps* ops = a->ops;
   const hipStream_t hs = (hipStream_t)stream;
-  const int rc = dispatch(st, a, dtype, [=](const void* rt) {
-    RolloutArgs o = ra;
-    o.P = dtype == ABRK_F64 ? (const void*)&p64 : (const void*)&p32;
-    o.K = dtype == ABRK_F64 ? (const void*)&k64 : (const void*)&k32;
-    return ops->rollout(dtype, LaunchArgs{rt, (long)B, hs}, o);
+  return with_status_word(st, pb, nullptr, [&] {
+    return dispatch(st, a, dtype, [=](const void* rt) {
+      RolloutArgs o = ra;
+      o.P = pb.of(dtype);
+      o.K = kb.of(dtype);
+      return ops->rollout(dtype, LaunchArgs{rt, (long)B, hs}, o);
+    });
   });
-  if (rc == 0 && st.staged && sw && sw->take()) return singular_error();
-  return rc;
 }
 
 // ------------------------------------------------------------------------------- launch plans
@@ -2280,13 +2188,21 @@ extern "C" int abrk_sliding_plan_create(int arm_id, int dtype, const abrk_slidin
   return abrk_plan_end();
 }
 
-extern "C" int abrk_plan_launch(int plan) {
-  Plan* pl = find_plan(plan);
-  if (!pl) return fail(ABRK_EINVAL, "unknown plan %d", plan);
+namespace {
+// make the plan's device current (plan launches skip hipSetDevice when this thread is already on it)
+int use_plan_device(const Plan* pl) {
   if (t_current_device != pl->device) {
     HIPCHK(hipSetDevice(pl->device));
     t_current_device = pl->device;
   }
+  return 0;
+}
+}  // namespace
+
+extern "C" int abrk_plan_launch(int plan) {
+  Plan* pl = find_plan(plan);
+  if (!pl) return fail(ABRK_EINVAL, "unknown plan %d", plan);
+  if (int rc = use_plan_device(pl)) return rc;
   HIPCHK(pl->enqueue());
   return 0;
 }
@@ -2295,10 +2211,7 @@ extern "C" int abrk_plan_launch_repeat(int plan, int repeat) {
   Plan* pl = find_plan(plan);
   if (!pl) return fail(ABRK_EINVAL, "unknown plan %d", plan);
   if (repeat < 1) return fail(ABRK_EINVAL, "repeat must be >= 1");
-  if (t_current_device != pl->device) {
-    HIPCHK(hipSetDevice(pl->device));
-    t_current_device = pl->device;
-  }
+  if (int rc = use_plan_device(pl)) return rc;
   for (int i = 0; i < repeat; i++) HIPCHK(pl->enqueue());
   return 0;
 }
@@ -2307,10 +2220,7 @@ extern "C" int abrk_plan_launch_graph(int plan, int repeat) {
   Plan* pl = find_plan(plan);
   if (!pl) return fail(ABRK_EINVAL, "unknown plan %d", plan);
   if (repeat < 1) return fail(ABRK_EINVAL, "repeat must be >= 1");
-  if (t_current_device != pl->device) {
-    HIPCHK(hipSetDevice(pl->device));
-    t_current_device = pl->device;
-  }
+  if (int rc = use_plan_device(pl)) return rc;
   if (!pl->stream) return fail(ABRK_EINVAL, "graph launches need a plan created on an explicit stream");
   if (pl->graph_repeat != repeat) {
     pl->drop_graph();
@@ -2376,25 +2286,21 @@ extern "C" int abrk_ik_generate_path_batch(int arm_id, int dtype, const abrk_ik_
   const size_t s = esz(dtype);
   const size_t T = (size_t)P->n_timesteps;
   Stager st{device, (hipStream_t)stream};
-  const void* q_ = st.add(position, B * n * s, true, false);
-  const void* t_ = st.add(target, B * 6 * s, true, false);
-  void* pp_ = st.add(position_path, B * T * n * s, false, true);
-  void* vp_ = st.add(velocity_path, B * T * n * s, false, true);
+  IkArgs ia{};
+  st.in(&ia.q, position, B * n * s);
+  st.in(&ia.target, target, B * 6 * s);
+  st.out(&ia.pp, position_path, B * T * n * s);
+  st.out(&ia.vp, velocity_path, B * T * n * s);
   if (int rc = st.reserve()) return rc;
-  IkArgs ia;
-  ia.q = st.fix(q_, position);
-  ia.target = st.fix(t_, target);
-  ia.pp = st.fix(pp_, position_path);
-  ia.vp = st.fix(vp_, velocity_path);
-  IkP<double> p64{P->max_dx * P->dt, P->max_dr * P->dt, P->max_dq * P->dt, P->n_timesteps, P->method};
-  IkP<float> p32{(float)(P->max_dx * P->dt), (float)(P->max_dr * P->dt), (float)(P->max_dq * P->dt), P->n_timesteps,
-                 P->method};
-  ia.P = nullptr;
+  const auto pb = blocks([&](auto t) {
+    using R = decltype(t);
+    return IkP<R>{R(P->max_dx * P->dt), R(P->max_dr * P->dt), R(P->max_dq * P->dt), P->n_timesteps, P->method};
+  });
   const ArmOps* ops = a->ops;
   const hipStream_t hs = (hipStream_t)stream;
   return dispatch(st, a, dtype, [=](const void* rt) {
     IkArgs o = ia;
-    o.P = dtype == ABRK_F64 ? (const void*)&p64 : (const void*)&p32;
+    o.P = pb.of(dtype);
     return ops->ik(dtype, LaunchArgs{rt, (long)B, hs}, o);
   });
 }

@@ -270,6 +270,25 @@ def test_gpu_singular_inertia_matrix_is_reported():
     ud = engine.osc_generate(good.arm_id, 6, laws[0], q_, dq_, t_, stream=s)
     s.sync()
     assert np.array_equal(ud.numpy(), good.osc(laws[0], q, dq, t)[0])
+    # host batches over shards (abrk_osc_generate_sharded): the call reports its own batch, x,y,z and six-row law alike
+    from abr_control_amd.sharding import MultiDevice
+
+    devices = [0, 0, 0]
+    for p in (laws[0], laws[2]):
+        with pytest.raises(np.linalg.LinAlgError) as ei:
+            engine.osc_generate_sharded(bad.arm_id, 6, p, q, dq, t, devices)
+        assert isinstance(ei.value, SingularMatrixError) and ei.value.code == _abi.ESINGULAR
+        us = engine.osc_generate_sharded(good.arm_id, 6, p, q, dq, t, devices)  # nothing sticks
+        assert np.array_equal(us, engine.osc_generate(good.arm_id, 6, p, q, dq, t))
+    # ... and nothing a resident call left on the library's shard streams (the same streams): that flag stays for the
+    # resident batch's own sync, which reports it once
+    md = MultiDevice(devices)
+    qs, dqs, ts_ = (md.scatter(x) for x in (q, dq, t))
+    engine.osc_generate_resident(bad.arm_id, 6, laws[0], qs, dqs, ts_)
+    engine.osc_generate_sharded(good.arm_id, 6, laws[0], q, dq, t, devices)
+    with pytest.raises(np.linalg.LinAlgError):
+        md.sync()
+    md.sync()
 
 
 def test_gpu_singular_flag_is_per_stream():
