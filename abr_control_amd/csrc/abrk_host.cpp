@@ -770,9 +770,9 @@ int with_status_word(const Stager& st, OscBlocks& pb, StatusWord* given, Run&& r
   return rc == 0 && own && sw && sw->take() ? singular_error() : rc;
 }
 
-// Worklist of the six-row OSC kernels (rows whose law needs the truncating pseudo-inverse are deferred to a second pass,
-// abrk_kernels.h): wl_ints(B) ~ B + 20 k ints of device scratch and - hand-over mode, batches of up to
-// kHandoverMaxRows - a record of rec_len(n) values per list slot.  Immediate calls take both from a cache keyed by
+// Scratch of the six-row OSC kernels (rows whose law needs the truncating pseudo-inverse are deferred to a second pass;
+// which form a batch takes: abrk_osc6_plan.h): wl_ints(B) ~ B + 20 k ints of device memory and - hand-over forms - a
+// record of rec_len(n) values per row.  Immediate calls take both from a cache keyed by
 // (device, stream) - calls on one stream are ordered, so the buffers can be reused - PROVIDED the launches that use
 // them (counters' memset, pass 1, pass 2) enter the stream as a unit: several host threads may share a stream (every
 // Python call without an explicit stream is on the NULL stream, and ctypes releases the GIL), and memset A, pass-1 A,
@@ -800,15 +800,7 @@ std::mutex g_wl_mu;
 std::vector<std::shared_ptr<WorklistSlot>> g_wl_cache;
 uint64_t g_wl_clock = 0;
 std::atomic<int64_t> g_wl_inline_fallbacks{0}, g_wl_evictions{0};
-// batches up to here take the hand-over form of the six-row law (kHandoverMaxRows is what the finish kernel can scan).
-// Measured on one box (UR5, all six rows, us per step, hand-over / recompute form): 4096 rows 17.1 / 20.9 (the recompute
-// form runs one-pass below 16 k rows), 16 k 18.3 / 32.6, 32 k 23.0 / 33.8, 64 k 35.9 / 37.0, 128 k 47.2 / 38.8, 256 k 67.8 /
-// 48.6 - beyond 64 k rows the deferred rows fill wavefronts, and re-running the row program on coalesced inputs beats
-// reading 656-byte records one lane each.
-constexpr int64_t kHandoverRows = 65536;
 constexpr size_t kWlCacheSlots = 64;
-// batches up to kHandoverRows (below) hand the deferred rows' intermediate results over to the second pass (43 MB of
-// records for a six-joint arm in fp64); beyond, the second pass recomputes its rows
 
 void wl_release(WorklistSlot& s) {  // caller holds s.mu; the slot's stream is drained
   (void)hipSetDevice(s.device);
@@ -844,31 +836,20 @@ void wl_forget_stream(int device, hipStream_t stream) {
   }
   if (mine) wl_retire(mine, true);  // (a caller that found the slot just before may still be enqueueing: s->mu)
 }
-// Beyond kHandoverRows and up to here the hand-over form continues with the DENSE finish kernel (abrk_law.hip
-// osc6_finish_dense_kernel, round 6: 64 chunks' records numbered through, one record per lane) instead of the recompute
-// pass.  Same box, UR5 six rows, us per step recompute / dense: 131 072 rows 36.9 / 29.5, 1 M rows 98.9 / 98.0, 8 M rows
-// 708 / 758 (profiles/round6/dense_finish_ab.txt): while the records (656 B per deferred row, written 16 bytes at a time
-// by ~3 lanes of a wavefront) stay in the caches they beat re-running the 1800-instruction kinematics; from HBM their
-// traffic - 2 x 253 MB at 8 M rows - costs more than the recomputation.
-constexpr int64_t kDenseFinishRows = 1 << 20;
-int64_t dense_finish_max() {
-  static const int64_t v = [] {  // measurement switch (0: recompute form beyond kHandoverRows, as until round 5)
-    const char* e = measurement_env("ABRK_DENSE_MAX");
-    return e ? (int64_t)atoll(e) : kDenseFinishRows;
+// the six-row law's measurement switches (abrk_osc6_plan.h), read once
+const Osc6Switches& osc6_switches() {
+  static const Osc6Switches sw = [] {
+    Osc6Switches s;
+    s.no_defer = measurement_env("ABRK_NO_DEFER") != nullptr;
+    s.no_handover = measurement_env("ABRK_NO_HANDOVER") != nullptr;
+    if (const char* e = measurement_env("ABRK_HANDOVER_MAX")) s.handover_max = atoll(e);
+    if (const char* e = measurement_env("ABRK_DENSE_MAX")) s.dense_max = atoll(e);
+    if (const char* e = measurement_env("ABRK_FINISH_SLOTS")) s.finish_slots = atoi(e);
+    if (const char* e = measurement_env("ABRK_FINISH_ROUNDS")) s.finish_rounds = atoi(e);
+    if (const char* e = measurement_env("ABRK_FINISH_GROUP")) s.finish_group = atoi(e);
+    return s;
   }();
-  return v;
-}
-int64_t handover_max() {  // the largest batch whose records go to the per-chunk / grouped finish kernels
-  static const int64_t v = [] {  // measurement switch
-    const char* e = measurement_env("ABRK_HANDOVER_MAX");
-    const int64_t x = e ? atoll(e) : kHandoverRows;
-    return x < kHandoverMaxRows ? x : (int64_t)kHandoverMaxRows;
-  }();
-  return v;
-}
-bool handover_enabled() {
-  static const bool off = measurement_env("ABRK_NO_HANDOVER") != nullptr;  // measurement switch: the round-3 scheme
-  return !off;
+  return sw;
 }
 // one of the slot's two buffers grown to `need` bytes (+ 25 %); the other one is left alone.  The slot's stream is
 // drained first if the old buffer may still be in use (every earlier user enqueued under s->mu).  false: no memory
@@ -890,22 +871,20 @@ bool wl_grow(hipStream_t stream, void** buf, size_t* cap, size_t need, bool* dra
   *cap = need + need / 4;
   return true;
 }
-// -> 0 and *wl = the worklist (nullptr: run the sweeps inline), *rec = the record store (nullptr: recompute form), or
-// an error code.  n / dtype: the arm's joint count and the arithmetic type (record size).
-int worklist_for(int device, hipStream_t stream, int64_t B, int n, int dtype, int** wl, void** rec, WlHold& hold) {
-  *wl = nullptr;
-  *rec = nullptr;
-  static const bool off = measurement_env("ABRK_NO_DEFER") != nullptr;  // measurement switch: sweeps inline, as before round 2
-  // (row indices are parked as 32-bit ints: batches beyond 2^31 rows - they fit the 288 GB for fp32 arms - run inline)
-  if (off || B > 0x7fffffffLL) return 0;
-  const int64_t ho_max = handover_max();
-  // below one wavefront of rows the second launch costs more than the eigen-decomposition it takes off the critical path
-  // (a single state truncates in 4.6 % of the calls: 0.7 us expected, against ~4 us of launch + the finish kernel's scan)
-  const bool handover = handover_enabled() && B >= 64 && (B <= ho_max || B <= dense_finish_max());
-  // the recompute form below ~16 k rows: the second launch costs more than the divergence it removes (round 2)
-  if (!handover && B < 16384) return 0;
+// The scratch a plan other than OnePass needs, of (device, stream) or owned by the plan being recorded: -> 0 and *wl =
+// the worklist / the chunks' masks, *rec = the record store (hand-over forms), or an error code.  An immediate call that
+// finds no scratch runs the sweeps inline (same results): `plan` is then OnePass, *wl and *rec stay null.
+// n / dtype: the arm's joint count and the arithmetic type (record size).
+int worklist_for(int device, hipStream_t stream, int64_t B, int n, int dtype, Osc6Plan& plan, int** wl, void** rec,
+                 WlHold& hold) {
+  const bool handover = plan.uses_records();
+  const auto inline_fallback = [&] {
+    g_wl_inline_fallbacks++;
+    plan = Osc6Plan{};
+    return 0;
+  };
   const size_t need = (size_t)wl_ints(B) * sizeof(int);
-  // (hand-over mode keeps one 64-bit mask per 64-row chunk in `wl` - far less than the recompute form's lists)
+  // (hand-over forms keep one 64-bit mask per 64-row chunk in `wl` - far less than the recompute form's lists)
   // (whole chunks: the finish kernel asks for a chunk's slot before it knows whether a record is there)
   const size_t need_rec = handover ? (size_t)((B + kBlock - 1) / kBlock * kBlock) * rec_len(n) * esz(dtype) : 0;
   if (Recorder* r = t_rec) {
@@ -951,10 +930,7 @@ int worklist_for(int device, hipStream_t stream, int64_t B, int n, int dtype, in
             }
           }
           (void)hipSetDevice(device);
-          if (pick == g_wl_cache.size()) {  // every cached stream is busy: inline sweeps for this call
-            g_wl_inline_fallbacks++;
-            return 0;
-          }
+          if (pick == g_wl_cache.size()) return inline_fallback();  // every cached stream is busy
           g_wl_evictions++;
           evicted = std::move(g_wl_cache[pick]);
           evicted_stream_alive = pick_alive;
@@ -976,8 +952,7 @@ int worklist_for(int device, hipStream_t stream, int64_t B, int n, int dtype, in
     if (s->retired) {  // evicted / forgotten between the look-up and the lock: look again (a fresh slot)
       hold.release();
       if (attempt < 4) continue;
-      g_wl_inline_fallbacks++;
-      return 0;
+      return inline_fallback();
     }
     bool drained = false;
     void* b = s->buf;
@@ -988,38 +963,12 @@ int worklist_for(int device, hipStream_t stream, int64_t B, int n, int dtype, in
     s->buf = (int*)b;
     if (!ok) {
       hold.release();
-      g_wl_inline_fallbacks++;
-      return 0;  // no scratch on an immediate call: inline sweeps (same results)
+      return inline_fallback();  // no memory
     }
     *wl = s->buf;
     if (handover) *rec = s->rec;
     return 0;
   }
-}
-
-// finish kernel of the hand-over form: measurement switches (read once)
-int env_int(const char* name, int dflt) {
-  const char* e = measurement_env(name);
-  return e ? atoi(e) : dflt;
-}
-// wavefronts per chunk and records per wavefront of the finish kernel (abrk_kernels.h finish_slots / finish_rounds);
-// measurement switches, read once
-int finish_slots_for(int64_t B) {
-  static const int forced = env_int("ABRK_FINISH_SLOTS", 0);
-  return forced >= 1 && forced <= kBlock ? forced : finish_slots((long)B);
-}
-// chunks per group of the grouped finish kernel (abrk_law.hip osc6_finish_group_kernel), 0 = the per-chunk kernel: the
-// 16384-row band, where the per-chunk grid doubles working wavefronts up on SIMDs
-int finish_group_for(int64_t B) {
-  if (B > handover_max()) return -1;  // (beyond that the hand-over form only exists with the dense finish kernel: worklist_for)
-  static const int forced = env_int("ABRK_FINISH_GROUP", -1);  // measurement switch: 0 = never grouped, 1..16 = always
-  if (forced >= 0 && forced <= 16) return forced;
-  const int64_t nchunk = (B + kBlock - 1) / kBlock;
-  return nchunk > 128 && nchunk <= 256 ? 16 : 0;
-}
-int finish_rounds_for(int64_t B) {
-  static const int forced = env_int("ABRK_FINISH_ROUNDS", -1);  // (0: every chunk goes one record per lane)
-  return forced >= 0 ? (forced > kBlock ? kBlock : forced) : finish_rounds((long)B);
 }
 
 int check_common(int arm_id, int dtype, int64_t B, ArmEntry** a) {
@@ -1164,21 +1113,25 @@ static int osc_generate_impl(int arm_id, int dtype, const abrk_osc_params* P, in
   oa.use_C = P->use_C ? 1 : 0;
   oa.fast = osc_fast_rows(*P, n, u_null_ext != nullptr);
   WlHold wl_hold;  // the (device, stream) worklist stays ours until the launches are enqueued
-  if (oa.fast == 0 && !want)
-    if (int rc = worklist_for(device, (hipStream_t)stream, B, n, dtype, &oa.wl, &oa.rec, wl_hold)) return rc;
+  Osc6Plan plan;
+  if (oa.fast == 0 && !want) {
+    plan = osc6_plan((long)B, osc6_switches());
+    if (plan.form != Osc6Form::OnePass)
+      if (int rc = worklist_for(device, (hipStream_t)stream, B, n, dtype, plan, &oa.wl, &oa.rec, wl_hold)) return rc;
+  }
+  oa.form = plan.form;
   auto pb = blocks([&](auto t) { return make_oscp<decltype(t)>(*P, n); });
   const ArmOps* ops = a->ops;
   const hipStream_t hs = (hipStream_t)stream;
-  // hand-over mode: the arm's first pass, then the arm-independent finish kernel on the records it left
-  FinishArgs fa{oa.wl, oa.rec, (P->n_null > 0 || u_null_ext) ? 1 : 0, finish_slots_for(B), finish_rounds_for(B),
-                oa.u, oa.ts, finish_group_for(B)};
+  // hand-over forms: the arm's first pass, then the arm-independent finish kernel on the records it left
+  const FinishArgs fa{plan, oa.wl, oa.rec, (P->n_null > 0 || u_null_ext) ? 1 : 0, oa.u, oa.ts};
   return with_status_word(st, pb, word, [&] {
     return dispatch(st, a, dtype, [=](const void* rt) {
       OscArgs o = oa;
       o.P = pb.of(dtype);
       const LaunchArgs la{rt, (long)B, hs};
       const hipError_t e = ops->osc(dtype, la, o);
-      if (e != hipSuccess || !o.rec) return e;
+      if (e != hipSuccess || !fa.plan.uses_records()) return e;
       return launch_osc6_finish(n, dtype, la, fa);
     }, &wl_hold);
   });

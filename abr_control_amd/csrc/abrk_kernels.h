@@ -4,11 +4,13 @@
 #pragma once
 #include <cstdlib>
 
+#include "abrk_osc6_plan.h"
 #include "abrk_rows.h"
 
 namespace abrk {
 
 constexpr int kBlock = 64;  // rows are independent, no LDS sharing: one wavefront per workgroup
+static_assert(kBlock == kOsc6ChunkRows, "the six-row plan counts chunks of one first-pass wavefront");
 constexpr int kMinWaves = 1;  // kernels without a register cap: whatever occupancy their register count allows
 // Measurement switches of the host-side launch logic (ABRK_NO_HANDOVER, ABRK_FINISH_SLOTS, ABRK_OBS_PLAIN, ...: listed in
 // INTEGRATION.md) are read only when ABRK_MEASUREMENT=1 is set: no stray environment variable changes which algorithm a
@@ -19,6 +21,15 @@ inline const char* measurement_env(const char* name) {
     return e && e[0] == '1';
   }();
   return on ? getenv(name) : nullptr;
+}
+
+// inclusive prefix sum of one count per lane over the wavefront (lane 63 holds the total)
+__device__ __forceinline__ int wave_scan_incl(int v, int lane) {
+  for (int d = 1; d < kBlock; d <<= 1) {
+    const int up = __shfl_up(v, d);
+    if (lane >= d) v += up;
+  }
+  return v;
 }
 
 #define ABRK_ROW_INDEX                                     \
@@ -353,132 +364,6 @@ osc_kernel(A arm, OscP<T> P, long B, const T* __restrict__ qg, const T* __restri
   }
 }
 
-// ---- second pass of the six-row law on hand-over records (osc_law6's deferral branch wrote them; abrk_device.h rec_*,
-// ScratchBase::record: the records of a 64-row chunk packed at the chunk's first slots, each carrying its row's index;
-// the arithmetic: abrk_ctrl.h osc6_rec_solve).  Which rows deferred arrives as one 64-bit mask per 64-row chunk (the
-// first pass's ballot).  The grid is (chunks, slots): wavefront (j, s) asks for chunk j's mask AND for the record in the
-// chunk's slot s at once - one memory round trip; whether there is such a record it learns from the mask's popcount.
-// (Round 4 began with a global compaction of all masks in every wavefront - a prefix sum, a second walk over the masks,
-// a row list in LDS - and the dependent chain mask -> row -> record: ~1.5 us of an 8.9 us kernel.)  Two forms, chosen
-// per chunk from its own count:
-//   * wave-cooperative (count <= coop_rounds x slots): wavefront (j, s) takes the chunk's records s, s + slots, ...
-//     Every lane decomposes the record's 6 x 6 Mx_inv - redundantly, so nothing crosses lanes and every data-dependent
-//     branch of the QL iteration is uniform (only the rotations that exist are executed: ~35 of the 68 slots the
-//     predicated per-lane form walks) - and applies the transformations to ITS column of [J | u_task | J v]; lanes N
-//     and N + 1 then hand their column to the others (v_readlane) and lane c < N finishes joint c.  A lone lane's
-//     eigen-decomposition was the critical path of every small six-row step (4096 rows: 95 % of the 64 wavefronts
-//     have a truncating row, 21 us per step of which ~15 us are ONE lane's 4800 dependent instructions); here the
-//     per-lane work is the scalar recurrence plus one vector, and a 4096-row step's ~190 such rows run on 190 of the
-//     1024 SIMDs at once.
-//   * one record per lane (more than that: arms whose Mx_inv always truncates, large batches where `slots` is small):
-//     wavefront (j, 0) takes all of the chunk's records, the same arithmetic with all N + 2 columns on the lane.
-// Both are the same solver with contraction pinned off: a row's bits do not depend on which ran.
-template <class T>
-__device__ __forceinline__ T lane_bcast(T v, int src) {
-  if constexpr (sizeof(T) == 8) {
-    const long long x = __builtin_bit_cast(long long, v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(x & 0xffffffffLL), src);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(x >> 32), src);
-    return __builtin_bit_cast(T, (long long)(((unsigned long long)hi << 32) | lo));
-  } else {
-    return __builtin_bit_cast(T, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), src));
-  }
-}
-// (keeps a value that was asked for ahead of a branch from being asked for behind it)
-template <class T>
-__device__ __forceinline__ void pin_loaded(T& v) {
-  asm volatile("" : "+v"(v));
-}
-// Workgroups are single wavefronts: the wave-cooperative form is bound by ONE wavefront's instruction stream, and two
-// of them on a SIMD halve each other's issue rate (measured with 512-thread workgroups: eight working wavefronts per
-// CU, 14.4 us for 190 rows; the dispatcher spreads single-wavefront workgroups over the CUs).  blockIdx.x is the chunk:
-// the wavefronts that have a record (slots 0, 1, 2 of most chunks) come first in dispatch order and spread over all XCDs.
-template <int N, class T>
-__global__ void __launch_bounds__(kBlock)
-osc6_finish_kernel(const unsigned long long* __restrict__ masks, const T* __restrict__ recs, int nulls, int coop_rounds,
-                   long B, T* __restrict__ ug, T* __restrict__ tsg) {
-  const int lane = (int)threadIdx.x;
-  const long j = blockIdx.x;
-  const int s0 = (int)blockIdx.y, slots = (int)gridDim.y;
-  const int c = lane < N + 2 ? lane : N + 1;  // (idle lanes shadow the last column)
-  const int jc = lane < N ? lane : 0;
-  const T* rec = recs + (j * kBlock + s0) * rec_len(N);
-  // mask and record together (the record's slot exists whatever it holds: the host sizes `recs` in whole chunks)
-  // (the mask through the vector memory path, like the record's columns: as a scalar load the compiler queues it behind
-  //  the wait for the record's scalar loads - two round trips again)
-  long jv = j;
-  pin_loaded(jv);
-  unsigned long long mask = masks[jv];
-  T S[21], G[1][6], ridx, b1, b2;
-  auto load = [&]() ABRK_LAMBDA {
-    osc6_rec_load<N, T, 1>(rec, c, S, G);
-    ridx = rec[21];
-    // the two joint-space sums are asked for with the rest of the record: one memory round trip, not two
-    b1 = rec[rec_off_b1(N) + jc];
-    b2 = rec[rec_off_b1(N) + N + jc];
-  };
-  load();
-  sfor<21>([&](auto e) ABRK_LAMBDA { pin_loaded(S[e()]); });
-  sfor<6>([&](auto r) ABRK_LAMBDA { pin_loaded(G[0][r()]); });
-  pin_loaded(ridx);
-  pin_loaded(b1);
-  pin_loaded(b2);
-  pin_loaded(mask);
-  const int cnt = __builtin_amdgcn_readfirstlane(__popcll(mask));
-  if (s0 >= cnt) return;  // nothing in this slot
-  if (cnt <= coop_rounds * slots) {
-    for (int s = s0;;) {
-      // (a record's row index is data: whatever a slot holds, nothing is stored outside [0, B))
-      const bool row_ok = ridx >= T(0) && ridx < T(B);
-      const long b = row_ok ? (long)ridx : 0;
-      {
-#pragma clang fp contract(off)  // the same bits as osc6_finish_row
-        T li[6], iq[6], y[6];
-        osc6_rec_solve<N, T, 1, true>(rec, c, S, G, li, iq);
-        ql_pinv_solve<6>(li, iq, G[0], y);  // this lane's column through the pseudo-inverse
-        T a1 = T(-0.0), a2 = T(-0.0);
-        sfor<6>([&](auto i) ABRK_LAMBDA {
-          const T yu = lane_bcast(y[i()], N), yw = lane_bcast(y[i()], N + 1);
-          a1 = Rm<T>::fma(G[0][i()], yu, a1);
-          a2 = Rm<T>::fma(G[0][i()], yw, a2);
-        });
-        if (lane < N && row_ok) {
-          const T ts = b1 - a1;
-          ug[b * N + lane] = ts + b2 - (nulls ? a2 : T(0));
-          if (tsg) tsg[b * N + lane] = ts;
-        }
-      }
-      s += slots;
-      if (s >= cnt) break;
-      rec = recs + (j * kBlock + s) * rec_len(N);
-      load();
-    }
-  } else if (s0 == 0 && lane < cnt) {
-    rec = recs + (j * kBlock + lane) * rec_len(N);
-    const T rix = rec[21];
-    if (rix >= T(0) && rix < T(B)) {
-      const long b = (long)rix;
-      T u[N], ts[N];
-      osc6_finish_row<N, T>(rec, nulls != 0, u, ts);
-      store_row<N>(ug, b, u);
-      if (tsg) store_row<N>(tsg, b, ts);
-    }
-  }
-}
-// Wavefronts per chunk and records a wavefront takes at most, by batch size (random UR5 states with all six task rows:
-// 4.6 % defer, 2.9 per chunk, more than 12 never).  Measured, us per step new / round-4 global compaction: 4096 rows
-// 15.6 / 16.4, 8192 15.7, 16 k 19.4 / 17.4, 32 k 20.2 / 23.0, 64 k 27.6 / 36.8.  Up to 8192 rows every (chunk, slot)
-// has a SIMD of its own; at 16 k rows the wavefronts of slots >= 4 share a SIMD with a working one (the finish kernel
-// lasts 12.0 us instead of 8.2 - the one size where compacting over the whole batch was better); beyond that the
-// working wavefronts outnumber the SIMDs anyway, a second round costs more than a second wavefront on the SIMD, and
-// chunks with more records than slots go one record per lane.
-inline int finish_slots(long B) {
-  const long nchunk = (B + kBlock - 1) / kBlock;
-  return nchunk <= 256 ? 12 : nchunk <= 512 ? 8 : 2;
-}
-inline int finish_rounds(long B) { return (B + kBlock - 1) / kBlock <= 256 ? 2 : 1; }
-constexpr long kHandoverMaxRows = 262144;  // (the finish kernel's grid: 4096 chunks x slots)
-
 // Mode F: u + Tx, J, M, g in one launch (840 B per UR5 row in fp64: HBM-bound).  One LDS slab serves both the
 // cooperative stores and (use_C) the scratch of the Coriolis recursion, which is dead by the time the first row is
 // parked.  FEAT is 0 (the plain law) or 2 (every optional input).
@@ -553,15 +438,13 @@ struct LaunchArgs {
   hipStream_t stream;
 };
 struct FinishArgs {
+  Osc6Plan plan;      // a Handover* form with its grid parameters (abrk_osc6_plan.h)
   const void* masks;  // one 64-bit mask per 64-row chunk: the rows the first pass deferred
   const void* rec;
   int nulls;
-  int slots;        // wavefronts per 64-row chunk (finish_slots)
-  int coop_rounds;  // records a wavefront takes at most; a chunk with more than slots x coop_rounds goes one record per lane
   void *u, *ts;
-  int group = 0;    // > 0: the grouped form - `group` chunks share 4 x group wavefronts (abrk_law.hip osc6_finish_group_kernel)
 };
-// (abrk_law.hip; arm-independent: the record holds everything)
+// (abrk_law.hip, kernels in abrk_finish.h; arm-independent: the record holds everything)
 hipError_t launch_osc6_finish(int n_joints, int dtype, const LaunchArgs& la, const FinishArgs& a);
 template <class A, class T, bool USE_C, int KM>
 __global__ void __launch_bounds__(kBlock, kMinWaves)
@@ -640,11 +523,7 @@ obstacles_lds_kernel(A arm, ObsP<T> P, long B, const T* __restrict__ qg, T* __re
     }
     // number the wavefront's pairs: lane l owns [pre, pre + cnt), in slot order
     const int cnt = __popcll(heavy);
-    int incl = cnt;
-    for (int d = 1; d < kBlock; d <<= 1) {
-      const int v = __shfl_up(incl, d);
-      if (lane >= d) incl += v;
-    }
+    const int incl = wave_scan_incl(cnt, lane);
     const int total = __builtin_amdgcn_readlane(incl, kBlock - 1);
     const int pre = incl - cnt;
     const int shared = total < kObsPairCap ? total : kObsPairCap;  // pairs [0, shared) are redistributed
@@ -773,9 +652,12 @@ struct OscArgs {
   int fast, use_C;  // fast: 0 general six-row kernel, 2 / 3: first two / three position rows of the EE
   const void *q, *dq, *target, *tv, *une;
   void *ierr, *u, *ts;
-  int* wl = nullptr;  // worklist of B + 1 ints: rows that need the Jacobi sweeps are deferred to a dense second pass
-  // hand-over records (rec_len(N) values per ROW): the first pass alone is launched, a deferred row leaves its record,
-  // `wl` receives one 64-bit mask per 64-row chunk, and the CALLER enqueues launch_osc6_finish behind it
+  // six-row kernels (abrk_osc6_plan.h).  Recompute: `wl` is the worklist (wl_ints(B) ints) - rows that need the Jacobi
+  // sweeps are deferred to a dense second pass.  Handover*: `rec` takes the records (rec_len(N) values per ROW), the first
+  // pass alone is launched, a deferred row leaves its record, `wl` receives one 64-bit mask per 64-row chunk, and the
+  // CALLER enqueues launch_osc6_finish behind it
+  Osc6Form form = Osc6Form::OnePass;
+  int* wl = nullptr;
   void* rec = nullptr;
   unsigned want = 0;  // != 0: the fused Mode-F kernel also writes Tx / J / M / g / C / dJ (W_TX | ... | W_DJ)
   void* out[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -862,10 +744,13 @@ struct Launch {
     };
     const bool nots = KM == 6 && FEAT == 0 && !a.ts;
     if constexpr (KM == 6) {
-      if (a.wl) {
+      if (a.form != Osc6Form::OnePass) {
+        const bool worklist = osc6_uses_worklist(a.form);
+        // (the kernel tells the two deferral modes apart by `rec`)
+        if (!a.wl || worklist != (a.rec == nullptr)) return hipErrorInvalidValue;
         // stale counters would let pass 1 append past its sub-lists: no launch without the memset (hand-over mode: no
         // counters - every chunk writes its mask)
-        if (!a.rec)
+        if (worklist)
           if (hipError_t e = hipMemsetAsync(a.wl, 0, 16 * kWlLists * sizeof(int), la.stream); e != hipSuccess) return e;
         dim3 g1 = grid_for(la.B);
         // (the persistent-grid form of the first pass: a multiple of kWlLists)
@@ -873,7 +758,7 @@ struct Launch {
         if (!plain && g1.x > kKm6GridCap) g1.x = kKm6GridCap;
         if (nots) go_nots(ic<1>{}, g1, 1);
         else go(ic<1>{}, g1, 1);
-        if (!a.rec) {  // a multiple of kWlLists: 8 blocks stride each sub-list
+        if (worklist) {  // a multiple of kWlLists: 8 blocks stride each sub-list
           if (nots) go_nots(ic<0>{}, dim3(8 * kWlLists), 2);
           else go(ic<0>{}, dim3(8 * kWlLists), 2);
         }

@@ -254,7 +254,8 @@ class HostsimBackend:
 class GpuBackend:
     """libabrk.so through the C ABI (abr_control_amd.engine) - static or runtime-table arm"""
 
-    # rows per call of the forms of the six-row law (abrk_host.cpp worklist_for / finish_group_for: one pass below one
+    # rows per call of the forms of the six-row law (csrc/abrk_osc6_plan.h osc6_plan; tests/test_osc6_plan.py checks that
+    # these sizes take the forms their names claim: one pass below one
     # wavefront of rows; hand-over records + per-chunk or grouped finish kernel up to 65 536 rows; hand-over records + the
     # dense finish kernel up to 1 048 576 rows; worklist + recompute pass beyond)
     ONE_PASS_ROWS, DENSE_ROWS, RECOMPUTE_ROWS = 48, 65536 + 128, (1 << 20) + 128
@@ -264,7 +265,7 @@ class GpuBackend:
         buffer gets (the plain six-row law then runs the `NOTS = true` instantiations); osc() returns (u, None).
         form: "auto" = one call on the rows as given; "slices" = calls of ONE_PASS_ROWS rows (the six-row law in one
         pass: `osc_kernel<.., PASS = 0>` in mode 0); "tiled" = the rows repeated up to DENSE_ROWS (first pass on hand-over
-        records, `PASS = 1` in mode 1, then the dense finish kernel, abrk_law.hip osc6_finish_dense_kernel); "recompute" =
+        records, `PASS = 1` in mode 1, then the dense finish kernel, abrk_finish.h osc6_finish_dense_kernel); "recompute" =
         the rows repeated up to RECOMPUTE_ROWS, beyond 1 M (first pass + recompute pass over the worklist: `PASS = 1` in
         mode 1, then `PASS = 0` in mode 2).  Tiled forms: every repetition bit-equal."""
         import ctypes as C

@@ -31,7 +31,7 @@ def build(force=False):
     srcs = [os.path.join(_HERE, "hostsim.cpp")] + [
         os.path.join(_CSRC, f)
         for f in ("abrk_device.h", "abrk_ctrl.h", "abrk_rows.h", "abrk_params.h", "abrk_rt.h", "abrk_arms_builtin.h",
-                  "abrk_sincos_table.h")]
+                  "abrk_sincos_table.h", "abrk_osc6_plan.h")]
     newest = max(os.path.getmtime(s) for s in srcs)
     procs = []
     for part, defs in PARTS.items():
@@ -239,6 +239,22 @@ def osc_mx(n, M, J, threshold=1e-3, dtype=np.float64):
                                            _p(Mx), _p(Minv))
     assert rc == 0, rc
     return Mx, Minv
+
+
+OSC6_FORMS = ("OnePass", "Recompute", "HandoverChunk", "HandoverGroup", "HandoverDense")
+_OSC6_SWITCHES = ("no_defer", "no_handover", "handover_max", "dense_max", "finish_slots", "finish_rounds", "finish_group")
+
+
+def osc6_plan(B, **switches):
+    """the form a six-row OSC call of B rows takes (csrc/abrk_osc6_plan.h `osc6_plan`); keyword arguments: members of
+    `Osc6Switches` (the measurement switches), the others keep what ships -> (form name, slots, rounds, group)"""
+    assert set(switches) <= set(_OSC6_SWITCHES), switches
+    given = sum(1 << i for i, k in enumerate(_OSC6_SWITCHES) if k in switches)
+    sw = (C.c_int64 * 7)(*[int(switches.get(k, 0)) for k in _OSC6_SWITCHES])
+    out = (C.c_int * 4)()
+    rc = _lib_for(law=True).hostsim_osc6_plan(C.c_int64(int(B)), C.c_uint(given), sw, out)
+    assert rc == 0, rc
+    return OSC6_FORMS[out[0]], out[1], out[2], out[3]
 
 
 def sym6_eig(A, method):

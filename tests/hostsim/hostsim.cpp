@@ -10,6 +10,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../../abr_control_amd/csrc/abrk_osc6_plan.h"
 #include "../../abr_control_amd/csrc/abrk_params.h"
 #include "../../abr_control_amd/csrc/abrk_rows.h"
 #include "../../abr_control_amd/csrc/abrk_rt.h"
@@ -337,6 +338,25 @@ extern "C" int hostsim_obstacles(const char* builtin, const abrk_arm_desc* d, in
 }
 
 #if HOSTSIM_LAW
+// the form a six-row OSC call of B rows takes (abrk_osc6_plan.h).  sw: no_defer, no_handover, handover_max, dense_max,
+// finish_slots, finish_rounds, finish_group - bit i of `given` set: sw[i] replaces what ships; out: form, slots, rounds, group
+extern "C" int hostsim_osc6_plan(int64_t B, unsigned given, const int64_t* sw, int* out) {
+  Osc6Switches s;
+  if (given & 1) s.no_defer = sw[0] != 0;
+  if (given & 2) s.no_handover = sw[1] != 0;
+  if (given & 4) s.handover_max = (long)sw[2];
+  if (given & 8) s.dense_max = (long)sw[3];
+  if (given & 16) s.finish_slots = (int)sw[4];
+  if (given & 32) s.finish_rounds = (int)sw[5];
+  if (given & 64) s.finish_group = (int)sw[6];
+  const Osc6Plan p = osc6_plan((long)B, s);
+  out[0] = (int)p.form;
+  out[1] = p.slots;
+  out[2] = p.rounds;
+  out[3] = p.group;
+  return 0;
+}
+
 extern "C" int hostsim_limits(int n, int dtype, const abrk_limits_params* P, int64_t B, const void* q, void* u,
                               int acc) {
 #define LIM_CASE(NN)                                                                                      \

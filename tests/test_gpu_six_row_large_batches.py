@@ -1,10 +1,11 @@
 """The six-row law (all six task rows: `osc6` / `osc5_j2` on the bench line) at the batch sizes where its launch form
-changes (abrk_host.cpp worklist_for / finish_group_for, abrk_kernels.h Launch::osc_launch):
+changes (csrc/abrk_osc6_plan.h osc6_plan - tests/test_osc6_plan.py holds it to this table -, abrk_kernels.h
+Launch::osc_launch):
 
     rows                  form
     < 64                  one pass (`osc_kernel<.., PASS = 0>`, mode 0)
     64 - 65 536           first pass (mode 1) + per-chunk or grouped finish kernel on hand-over records
-    65 537 - 1 048 576    first pass (mode 1) + dense finish kernel (abrk_law.hip osc6_finish_dense_kernel)
+    65 537 - 1 048 576    first pass (mode 1) + dense finish kernel (abrk_finish.h osc6_finish_dense_kernel)
     > 1 048 576           first pass (mode 1) + recompute pass over the worklist (`PASS = 0`, mode 2)
 
 The first pass of every kernel other than the plain law's two-waves-per-SIMD form is a persistent grid of at most
@@ -32,7 +33,7 @@ pytestmark = pytest.mark.gpu
 GROUP = 4096  # rows of one group of the dense finish kernel (64 chunks of 64 rows)
 WIN = cases.GpuBackend.ONE_PASS_ROWS  # rows of a one-pass call
 GRID_ROWS = 4096 * 64  # kKm6GridCap blocks of 64 rows: where a persistent first pass starts its second iteration
-DENSE_TOP = 1 << 20  # kDenseFinishRows: the largest batch of the dense finish form
+DENSE_TOP = 1 << 20  # Osc6Switches::dense_max: the largest batch of the dense finish form
 SIX = cases.SIX
 
 # the six-row settings of the existing suite (bench.py osc6 / osc5_j2, cases.check_six_row_near_singular,

@@ -119,23 +119,23 @@ int main(int argc, char** argv) {
     oa.ierr = nullptr;
     oa.u = u_;
     oa.ts = ts_;
+    // the product's plan for the batch; beyond 65 536 rows the recompute form, or (AB_DENSE) the dense finish kernel
+    Osc6Switches sw;
 #ifdef AB_DENSE
-    const bool handover = AB_KM == 6 && B >= 64;  // beyond 65 536 rows: hand-over records + the dense finish kernel
+    sw.dense_max = 0x7fffffffL;
 #else
-    const bool handover = AB_KM == 6 && B >= 64 && B <= 65536;
+    sw.dense_max = 0;
 #endif
+    const Osc6Plan plan = AB_KM == 6 ? osc6_plan(B, sw) : Osc6Plan{};
+    const bool handover = plan.uses_records();
+    oa.form = plan.form;
     FinishArgs fa{};
-    if (AB_KM == 6 && B >= 64) {
+    if (plan.form != Osc6Form::OnePass) {
       CK(hipMalloc(&oa.wl, wl_ints(B) * sizeof(int) + 4096));
       CK(hipMemset(oa.wl, 0, wl_ints(B) * sizeof(int)));
       if (handover) {
-        CK(hipMalloc(&oa.rec, (size_t)B * rec_len(N) * sizeof(T)));
-        const long nchunk = (B + kBlock - 1) / kBlock;
-        fa = FinishArgs{oa.wl, oa.rec, AB_FEAT >= 1 ? 1 : 0, finish_slots(B), finish_rounds(B), oa.u, oa.ts,
-                        nchunk > 128 && nchunk <= 256 ? 16 : 0};
-#ifdef AB_DENSE
-        fa.dense = B > 65536;
-#endif
+        CK(hipMalloc(&oa.rec, (size_t)((B + kBlock - 1) / kBlock * kBlock) * rec_len(N) * sizeof(T)));
+        fa = FinishArgs{plan, oa.wl, oa.rec, AB_FEAT >= 1 ? 1 : 0, oa.u, oa.ts};
       }
     }
     const LaunchArgs la{nullptr, B, st};

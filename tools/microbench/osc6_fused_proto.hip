@@ -1,7 +1,7 @@
 // Prototype: the six-row law's small-batch step as ONE launch (profiles/round4/NOTES.md "what is left" item 2).
 //
 // Today a 4096-row step of the six-row law is two kernels: the first pass (osc_kernel<.., PASS = 1>: a deferring row
-// leaves a hand-over record, one ballot mask per 64-row chunk) and the finish kernel (osc6_finish_kernel: wavefront
+// leaves a hand-over record, one ballot mask per 64-row chunk) and the finish kernel (abrk_finish.h osc6_finish_kernel: wavefront
 // (chunk, slot) decomposes one record's Mx_inv).  15.6 us = 7.8 + 8.1, of which the finish kernel's own arithmetic is
 // 3.6 us: the rest of it is a launch gap (1.0 us between dependent kernel nodes of a graph replay), its ramp, and a
 // memory round trip that only starts when the kernel does.
@@ -24,7 +24,7 @@
 #include <random>
 #include <vector>
 
-#include "abrk_kernels.h"
+#include "abrk_finish.h"
 #include "abrk_params.h"
 
 using namespace abrk;
@@ -39,73 +39,6 @@ using namespace abrk;
   } while (0)
 
 constexpr int kSpinLimit = 1 << 20;  // polls of ~1 us each at the longest: a second, then the error flag
-
-// the finish role for (chunk j, slot s0): the body of osc6_finish_kernel (abrk_kernels.h), mask and record asked for
-// together once the chunk is published
-template <int N, class T>
-__device__ __forceinline__ void finish_role(long j, int s0, int slots, const unsigned long long* __restrict__ masks,
-                                            const T* __restrict__ recs, int nulls, int coop_rounds, long B,
-                                            T* __restrict__ ug, T* __restrict__ tsg) {
-  const int lane = (int)threadIdx.x;
-  const int c = lane < N + 2 ? lane : N + 1;
-  const int jc = lane < N ? lane : 0;
-  const T* rec = recs + (j * kBlock + s0) * rec_len(N);
-  long jv = j;
-  pin_loaded(jv);
-  unsigned long long mask = masks[jv];
-  T S[21], G[1][6], ridx, b1, b2;
-  auto load = [&]() ABRK_LAMBDA {
-    osc6_rec_load<N, T, 1>(rec, c, S, G);
-    ridx = rec[21];
-    b1 = rec[rec_off_b1(N) + jc];
-    b2 = rec[rec_off_b1(N) + N + jc];
-  };
-  load();
-  sfor<21>([&](auto e) ABRK_LAMBDA { pin_loaded(S[e()]); });
-  sfor<6>([&](auto r) ABRK_LAMBDA { pin_loaded(G[0][r()]); });
-  pin_loaded(ridx);
-  pin_loaded(b1);
-  pin_loaded(b2);
-  pin_loaded(mask);
-  const int cnt = __builtin_amdgcn_readfirstlane(__popcll(mask));
-  if (s0 >= cnt) return;
-  if (cnt <= coop_rounds * slots) {
-    for (int s = s0;;) {
-      const bool row_ok = ridx >= T(0) && ridx < T(B);
-      const long b = row_ok ? (long)ridx : 0;
-      {
-#pragma clang fp contract(off)
-        T li[6], iq[6], y[6];
-        osc6_rec_solve<N, T, 1, true>(rec, c, S, G, li, iq);
-        ql_pinv_solve<6>(li, iq, G[0], y);  // this lane's column through the pseudo-inverse
-        T a1 = T(-0.0), a2 = T(-0.0);
-        sfor<6>([&](auto i) ABRK_LAMBDA {
-          const T yu = lane_bcast(y[i()], N), yw = lane_bcast(y[i()], N + 1);
-          a1 = Rm<T>::fma(G[0][i()], yu, a1);
-          a2 = Rm<T>::fma(G[0][i()], yw, a2);
-        });
-        if (lane < N && row_ok) {
-          const T ts = b1 - a1;
-          ug[b * N + lane] = ts + b2 - (nulls ? a2 : T(0));
-          if (tsg) tsg[b * N + lane] = ts;
-        }
-      }
-      s += slots;
-      if (s >= cnt) break;
-      rec = recs + (j * kBlock + s) * rec_len(N);
-      load();
-    }
-  } else if (s0 == 0 && lane < cnt) {
-    rec = recs + (j * kBlock + lane) * rec_len(N);
-    const T rix = rec[21];
-    if (rix >= T(0) && rix < T(B)) {
-      T u[N], ts[N];
-      osc6_finish_row<N, T>(rec, nulls != 0, u, ts);
-      store_row<N>(ug, (long)rix, u);
-      if (tsg) store_row<N>(tsg, (long)rix, ts);
-    }
-  }
-}
 
 template <class A, class T, bool USE_C, int FEAT, bool NOTS>
 __global__ void __launch_bounds__(kBlock, 2)
@@ -155,7 +88,8 @@ osc6_fused_kernel(A arm, OscP<T> P, long B, const T* __restrict__ qg, const T* _
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    finish_role<A::N, T>(j, s0, slots, masks, rec, nulls, coop_rounds, B, ug, tsg);
+    // the finish role for (chunk j, slot s0): mask and record asked for together once the chunk is published
+    osc6_finish_chunk<A::N, T>(j, s0, slots, masks, rec, nulls, coop_rounds, B, ug, tsg);
     if (lane == 0) __hip_atomic_fetch_add(ready + j, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
@@ -209,7 +143,11 @@ static void run(long B, int K, FILE* out, bool last) {
   for (int r = 0; r < 6; r++) hp.ctrlr_dof[r] = 1;
   hp.ref_frame = 2 * N + 1;
   const OscP<T> P = make_oscp<T>(hp, N);
-  const int slots = finish_slots(B), rounds = finish_rounds(B);
+  Osc6Switches sw;
+  sw.finish_group = 0;  // (this tool launches the per-chunk finish kernel itself)
+  const Osc6Plan plan = osc6_plan(B, sw);
+  if (plan.form != Osc6Form::HandoverChunk) exit(3);
+  const int slots = plan.slots, rounds = plan.rounds;
 
   hipStream_t st;
   CK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));

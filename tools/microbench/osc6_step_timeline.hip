@@ -12,7 +12,7 @@
 #include <random>
 #include <vector>
 
-#include "abrk_kernels.h"
+#include "abrk_finish.h"
 #include "abrk_params.h"
 
 using namespace abrk;
@@ -67,7 +67,11 @@ static void run(long B, int K, FILE* out, bool last) {
   for (int r = 0; r < 6; r++) hp.ctrlr_dof[r] = 1;
   hp.ref_frame = 2 * N + 1;
   const OscP<T> P = make_oscp<T>(hp, N);
-  const int slots = finish_slots(B), rounds = finish_rounds(B);
+  Osc6Switches sw;
+  sw.finish_group = 0;  // (this tool launches the per-chunk finish kernel itself)
+  const Osc6Plan plan = osc6_plan(B, sw);
+  if (plan.form != Osc6Form::HandoverChunk) exit(3);
+  const int slots = plan.slots, rounds = plan.rounds;
   hipStream_t st;
   CK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
   auto step = [&](int k) {

@@ -9,7 +9,7 @@ here=$(cd "$(dirname "$0")/.." && pwd)
 case $hdr in /*) ;; *) hdr=$here/$hdr;; esac
 flags="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-signed-zeros -ffinite-math-only -mllvm -amdgpu-sched-strategy=max-ilp -fno-slp-vectorize"
 cat > $out.hip <<SRC
-#include "abrk_kernels.h"
+#include "abrk_finish.h"
 namespace abrk {
 template __global__ void $inst(${ARGS:-StaticArm<Tab_ur5>, OscP<double>, long, const double*, const double*, const double*, const double*, double*, const double*, double*, double*, int, int*, double*});
 }
