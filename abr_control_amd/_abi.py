@@ -205,6 +205,20 @@ def make_twolink_plant(L, M_LINKS, dt=0.001):
     return p
 
 
+class PlantParams(C.Structure):
+    """abrk_plant_params (include/abrk.h)"""
+    _fields_ = [("dt", C.c_double), ("substeps", C.c_int32), ("gravity", C.c_int32)]
+
+
+def make_plant_params(dt, substeps=1, gravity=True):
+    """One plant step of `dt`, taken as `substeps` Euler steps of dt / substeps with the torques held."""
+    p = PlantParams()
+    p.dt = float(dt)
+    p.substeps = int(substeps)
+    p.gravity = int(bool(gravity))
+    return p
+
+
 TABLE_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "arms", "tables")
 BUILTIN_ARMS = ("ur5", "jaco2", "twojoint", "threejoint", "onejoint")
 

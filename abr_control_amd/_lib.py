@@ -95,6 +95,9 @@ def lib():
         L.abrk_ik_generate_path_batch.argtypes = [C.c_int, C.c_int, C.POINTER(_abi.IkParams), _i64, _vp, _vp, _vp, _vp,
                                                   C.c_int, _vp]
         L.abrk_twolink_step_batch.argtypes = [C.c_int, C.POINTER(_abi.TwoLinkPlant), _i64, _vp, _vp, _vp, C.c_int, _vp]
+        L.abrk_forward_dynamics_batch.argtypes = [C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp]
+        L.abrk_plant_step_batch.argtypes = [C.c_int, C.c_int, C.POINTER(_abi.PlantParams), _i64, _vp, _vp, _vp,
+                                            C.c_int, _vp]
         L.abrk_osc_rollout_twolink_batch.argtypes = [
             C.c_int, C.c_int, C.POINTER(_abi.OSCParams), C.POINTER(_abi.TwoLinkPlant), _i64, C.c_int32, C.c_int32,
             _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]

@@ -1,5 +1,6 @@
 """Arm configs with the reference's `robot_config` API (abr_control/arms)."""
 from . import jaco2, onejoint, threejoint, twojoint, ur5  # noqa: F401
+from .arm_sim import ArmSim  # noqa: F401
 from .base_config import BatchedConfig  # noqa: F401
 
 

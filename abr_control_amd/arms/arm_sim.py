@@ -1,0 +1,49 @@
+"""Rigid-body plant of ANY arm with the reference's ArmSim interface (abr_control/arms/twojoint/arm_sim.py:20-87):
+connect / disconnect / reset / get_feedback / send_forces, for one arm (q of shape (n,)) or B arms (q_init of shape
+(B, n)), stepped on the GPU by engine.plant_step: ddq = M^-1 (u - C dq - g) with the robot_config's own M, C and g, then
+dq += ddq h, q += dq h, `substeps` times per call with h = dt / substeps (arms/threejoint/arm_sim.py:93-94 takes
+dt / 1e-5 such substeps).  No joint friction, joint limits or contacts."""
+import numpy as np
+
+from .. import _abi, engine
+
+
+class ArmSim:
+    def __init__(self, robot_config, dt=0.001, q_init=None, substeps=1, gravity=True):
+        self.robot_config = robot_config
+        n = robot_config.N_JOINTS
+        q0 = q_init if q_init is not None else getattr(robot_config, "START_ANGLES", None)
+        self.q_init = np.zeros(n) if q0 is None else np.array(q0, dtype=float)
+        if self.q_init.ndim not in (1, 2) or self.q_init.shape[-1] != n:
+            raise ValueError(f"q_init has shape {self.q_init.shape}; expected ({n},) or (B, {n})")
+        self.dt = dt
+        self.substeps = int(substeps)
+        self.gravity = bool(gravity)
+        self.t = 0.0
+        self.reset()
+
+    def connect(self):
+        self.reset()
+
+    def disconnect(self):
+        self.reset()
+
+    def reset(self):
+        self.q = np.copy(self.q_init)
+        self.dq = np.zeros(self.q.shape)
+
+    def get_feedback(self):
+        return {"q": self.q, "dq": self.dq}
+
+    def send_forces(self, u, dt=None):
+        """advance one time step under torques u (arm_sim.py:67-82)"""
+        rc = self.robot_config
+        dtype = np.dtype(getattr(rc, "dtype", np.float64))
+        single = self.q.ndim == 1
+        q = np.array(np.atleast_2d(self.q), dtype=dtype, order="C")
+        dq = np.array(np.atleast_2d(self.dq), dtype=dtype, order="C")
+        u2 = np.ascontiguousarray(np.broadcast_to(np.atleast_2d(np.asarray(u, dtype=dtype)), q.shape))
+        params = _abi.make_plant_params(self.dt if dt is None else dt, self.substeps, self.gravity)
+        engine.plant_step(rc.arm_id, rc.N_JOINTS, params, q, dq, u2, dtype=dtype, device=rc.device)
+        self.q, self.dq = (q[0], dq[0]) if single else (q, dq)
+        self.t += self.dt

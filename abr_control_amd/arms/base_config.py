@@ -216,6 +216,18 @@ class BatchedConfig:
             res = {k: v[0] for k, v in res.items()}
         return res
 
+    def forward_dynamics(self, q, dq, u):
+        """Batched extension: joint accelerations ddq = M^-1 (u - C dq - g) under the torques u; (n,) or (B, n) in, the
+        same shape out, in the config's dtype."""
+        q2, dq2, single, dev = self._prep(q, dq)
+        if dev:
+            return engine.forward_dynamics(self.arm_id, self.N_JOINTS, q2, dq2, u, None, self.dtype, self.device)
+        u2 = np.atleast_2d(np.asarray(u, dtype=self.dtype))
+        if dq2.shape != q2.shape or u2.shape != q2.shape:
+            raise ValueError(f"q {q2.shape}, dq {dq2.shape} and u {u2.shape} must have one shape")
+        res = engine.forward_dynamics(self.arm_id, self.N_JOINTS, q2, dq2, u2, None, self.dtype, self.device)
+        return res[0] if single else res
+
     # ---- the reference's wrappers (base_config.py:210-415)
     def g(self, q):
         """force of gravity in joint space (base_config.py:210-223)"""

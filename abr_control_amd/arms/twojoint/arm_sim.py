@@ -9,6 +9,9 @@ from ... import _abi, engine
 
 
 class ArmSim:
+    """The reference's own closed form (thin rods, no gravity): a different model from the rigid-body dynamics of
+    twojoint.Config, which abr_control_amd.arms.ArmSim integrates for any arm - the two are not expected to agree."""
+
     def __init__(self, robot_config, dt=0.001, q_init=None):
         self.robot_config = robot_config
         self.q_init = np.array(q_init if q_init is not None else robot_config.START_ANGLES, dtype=float)

@@ -2058,6 +2058,95 @@ ABRK_INL void twolink_step(const TwoLinkP<T>& K, T (&q)[2], T (&dq)[2], const T 
   q[1] += dq[1] * K.dt;
 }
 
+// ---------------------------------------------------------------- rigid-body plant of any arm, one row
+// Forward dynamics ddq = M^-1 (u - C(q,dq) dq - g) with M, g, C as robot_config.M / .g / .C return them, and
+// semi-implicit Euler steps in the reference's update order (arms/twojoint/arm_sim.py:131-132): dq += ddq h, then
+// q += dq h.  `substeps` steps of h with u held; the state stays in registers between them.
+// The dynamics pass is the one of the OSC(use_C) kernels of the arm's class (osc_row): the body recursion with the
+// wrenches in `scr` on orthogonal chains (kRecursiveC), the per-link Coriolis vector otherwise (general chains,
+// general-inertia arms, runtime tables).
+// integrate = false: one evaluation, ddq alone (q, dq untouched).  minpiv: the smallest real Cholesky pivot of M over
+// the substeps (chol above) - <= 0 is the reference's LinAlgError.
+template <class T>
+struct PlantP {
+  T h;  // dt / substeps, formed once on the host
+  int substeps, gravity, mode;
+  int* status;  // as OscP::status
+};
+// sin / cos of an angle beyond the fast routines' range (|x| >= 1e5), out of line: inlined into the substep loop, the
+// library routine's table reads are hoisted in front of the loop and held (spilled) across the whole row program
+template <class T>
+struct SinCosPair {
+  T s, c;
+};
+template <class T>
+ABRK_HD __attribute__((noinline)) SinCosPair<T> sincos_out_of_line(T x) {
+  SinCosPair<T> r;
+  Rm<T>::sincos(x, r.s, r.c);
+  return r;
+}
+template <class A, class T, class GetU, class Scr>
+ABRK_INL void plant_row(const A& arm, T h, int substeps, bool gravity, bool integrate, T (&q)[A::N], T (&dq)[A::N],
+                        GetU&& get_u, T (&ddq)[A::N], T& minpiv, Scr& scr) {
+  constexpr int N = A::N;
+  constexpr bool REC = kRecursiveC<A, CMODE_VEC>;
+  for (int s = 0; s < substeps; s++) {
+    // the main path of sincos_all_tab / sincos_all (the same bits as the OSC kernels' pass)
+    T sv[N][2];
+    bool all_in = true;
+    sfor<N>([&](auto i) ABRK_LAMBDA {
+      if constexpr (std::remove_reference<Scr>::type::kHasTab) {
+        all_in = all_in && Rm<T>::sincos_tab_in_range(q[i()]);
+        Rm<T>::sincos_tab(q[i()], scr.sctab, sv[i()][0], sv[i()][1]);
+      } else {
+        all_in = all_in && Rm<T>::sincos_in_range(q[i()]);
+        Rm<T>::sincos_fast(q[i()], sv[i()][0], sv[i()][1]);
+      }
+    });
+    if (!all_in)
+      sfor<N>([&](auto i) ABRK_LAMBDA {
+        const SinCosPair<T> r = sincos_out_of_line(q[i()]);
+        sv[i()][0] = r.s;
+        sv[i()][1] = r.c;
+      });
+    const ScUse<T, N> sincos_policy{sv};
+    Joints<A, T> jt;
+    Dyn<A, T, REC ? CMODE_NONE : CMODE_VEC> d;
+    T XR[9], xo[3], cv2[REC ? N : 1];
+    NoCap nc;
+    if constexpr (REC) {
+      RneState<T> rne;
+      rne_init(rne);
+      kin_dyn_hook(arm, q, dq, jt, d, XR, xo, nc, [&](auto L, const T(&pl)[3]) ABRK_LAMBDA {
+        ABRK_SCHED_FENCE();
+        rne_forward_step<L()>(arm, jt, pl, dq, rne, scr);
+        ABRK_SCHED_FENCE();
+      }, sincos_policy);
+      rne_backward(jt, scr, cv2);
+    } else {
+      kin_dyn_hook(arm, q, dq, jt, d, XR, xo, nc, [](auto, const T(&)[3]) ABRK_LAMBDA {}, sincos_policy);
+    }
+    ABRK_SCHED_FENCE();
+    // rhs = u - C dq - g with g = -9.81 gz: explicit operations, one rounding each (no contraction to decide)
+    T rhs[N], y[N], u[N];
+    get_u(u);
+    sfor<N>([&](auto i) ABRK_LAMBDA {
+      if constexpr (REC) rhs[i()] = Rm<T>::fma(T(-1), cv2[i()], u[i()]);
+      else rhs[i()] = Rm<T>::fma(T(-1), d.cv[i()], u[i()]);
+    });
+    if (gravity) sfor<N>([&](auto i) ABRK_LAMBDA { rhs[i()] = Rm<T>::fma(T(9.81), d.gz[i()], rhs[i()]); });
+    T L[N * (N + 1) / 2], il[N];
+    chol<N, T, false>(d.Ms, L, il, &minpiv);
+    chol_fwd<N>(L, il, rhs, y);
+    chol_bwd<N>(L, il, y, ddq);
+    if (!integrate) break;
+    sfor<N>([&](auto i) ABRK_LAMBDA {
+      dq[i()] = Rm<T>::fma(ddq[i()], h, dq[i()]);
+      q[i()] = Rm<T>::fma(dq[i()], h, q[i()]);
+    });
+  }
+}
+
 // ---------------------------------------------------------------- InverseKinematics.generate_path, one row
 // (controllers/path_planners/inverse_kinematics.py:84-135): n_steps sequential iterations, q in registers.
 template <class A, class T>

@@ -1999,6 +1999,78 @@ extern "C" int abrk_osc_rollout_twolink_batch(int arm_id, int dtype, const abrk_
   });
 }
 
+// ------------------------------------------------------------------------------- rigid-body plant of any arm
+namespace {
+template <class T>
+PlantP<T> make_plantp(double h, int substeps, int gravity, int mode) {
+  PlantP<T> p;
+  p.h = T(h);
+  p.substeps = substeps;
+  p.gravity = gravity;
+  p.mode = mode;
+  p.status = nullptr;
+  return p;
+}
+// Is the double at `p` a finite number > 0?  The library is built with -ffinite-math-only, under which the compiler
+// folds std::isfinite, NaN compares and even an exponent test of a value it knows to be a double: the bits are read
+// through an integer the optimiser is kept away from.
+__attribute__((noinline, optnone)) bool positive_finite_at(const void* p) {
+  volatile uint64_t b;
+  memcpy(const_cast<uint64_t*>(&b), p, sizeof(uint64_t));
+  const uint64_t v = b;
+  const bool finite = ((v >> 52) & 0x7ff) != 0x7ff, negative = (v >> 63) != 0, zero = (v << 1) == 0;
+  return finite && !negative && !zero;
+}
+// mode 0: ddq out, q / dq read; mode 1: q / dq in place
+int plant_impl(int arm_id, int dtype, int mode, double dt, int substeps, int gravity, int64_t B, void* q, void* dq,
+               const void* u, void* ddq, int device, void* stream) {
+  ArmEntry* a;
+  if (int rc = check_common(arm_id, dtype, B, &a)) return rc;
+  if (!a->ops->plant) return fail(ABRK_EINVAL, "this arm's kernels carry no plant (rebuild its plugin)");
+  if (!q || !dq || !u || (mode == 0 && !ddq)) return fail(ABRK_EINVAL, "q, dq, u%s are required", mode == 0 ? ", ddq" : "");
+  if (B == 0) return 0;
+  if (int rc = use_device(device)) return rc;
+  const int n = a->desc.n_joints;
+  const size_t bytes = (size_t)B * n * esz(dtype);
+  Stager st{device, (hipStream_t)stream};
+  PlantArgs pa{};
+  if (mode == 0) {
+    st.bind(&pa.q, q, bytes, true, false);
+    st.bind(&pa.dq, dq, bytes, true, false);
+  } else {
+    st.inout(&pa.q, q, bytes);
+    st.inout(&pa.dq, dq, bytes);
+  }
+  st.in(&pa.u, u, bytes);
+  st.out(&pa.ddq, mode == 0 ? ddq : nullptr, bytes);
+  if (int rc = st.reserve()) return rc;
+  auto pb = blocks([&](auto t) { return make_plantp<decltype(t)>(dt / substeps, substeps, gravity, mode); });
+  const ArmOps* ops = a->ops;
+  const hipStream_t hs = (hipStream_t)stream;
+  return with_status_word(st, pb, nullptr, [&] {
+    return dispatch(st, a, dtype, [=](const void* rt) {
+      PlantArgs o = pa;
+      o.P = pb.of(dtype);
+      return ops->plant(dtype, LaunchArgs{rt, (long)B, hs}, o);
+    });
+  });
+}
+}  // namespace
+
+extern "C" int abrk_forward_dynamics_batch(int arm_id, int dtype, int64_t B, const void* q, const void* dq,
+                                           const void* u, void* ddq, int device, void* stream) {
+  return plant_impl(arm_id, dtype, 0, 1.0, 1, 1, B, const_cast<void*>(q), const_cast<void*>(dq), u, ddq, device, stream);
+}
+
+extern "C" int abrk_plant_step_batch(int arm_id, int dtype, const abrk_plant_params* P, int64_t B, void* q, void* dq,
+                                     const void* u, int device, void* stream) {
+  if (!get_arm(arm_id)) return fail(ABRK_ENOARM, "unknown arm id %d", arm_id);
+  if (!P) return fail(ABRK_EINVAL, "params is NULL");
+  if (!positive_finite_at(&P->dt)) return fail(ABRK_EINVAL, "dt=%g is not a positive finite step", P->dt);
+  if (P->substeps < 1) return fail(ABRK_EINVAL, "substeps=%d < 1", P->substeps);
+  return plant_impl(arm_id, dtype, 1, P->dt, P->substeps, P->gravity ? 1 : 0, B, q, dq, u, nullptr, device, stream);
+}
+
 // ------------------------------------------------------------------------------- launch plans
 // A plan is the list of kernel launches recorded between abrk_plan_begin and abrk_plan_end (one control tick: one
 // law, or several secondary controllers accumulating into the buffer the OSC law then filters).  Launching it only

@@ -462,6 +462,32 @@ twolink_step_kernel(TwoLinkP<T> K, long B, T* __restrict__ qg, T* __restrict__ d
   twolink_step_body<T>(b, K, qg, dqg, ug);
 }
 
+// The rigid-body plant (abrk_ctrl.h plant_row): forward dynamics (P.mode 0) or P.substeps Euler steps with the state in
+// registers (P.mode 1).  One instantiation per (arm, type): substeps, gravity and mode are runtime and uniform.  The row
+// is the dynamics pass of the OSC(use_C) kernel plus one N x N solve, so it is asked for that kernel's budget: two waves
+// per SIMD on orthogonal chains (the recursion's wrenches in the LDS slab), whatever the registers allow on general chains
+// and runtime tables (osc_min_waves).
+template <class A>
+constexpr bool plant_uses_slab() { return kRecursiveC<A, CMODE_VEC>; }
+template <class A, class T>
+__global__ void __launch_bounds__(kBlock, osc_min_waves(3, true, 0, osc_ortho<A>(), 0, A::kStatic))
+plant_kernel(A arm, PlantP<T> P, long B, T* __restrict__ qg, T* __restrict__ dqg, const T* __restrict__ ug,
+             T* __restrict__ ddqg) {
+  constexpr bool kLds = plant_uses_slab<A>();
+  using V2 = typename LdsScratch<T, A::N>::V2;
+  __shared__ T sctab[2 * kSinCosN];
+  load_sincos_table(sctab, (int)threadIdx.x);  // every lane takes part: before any exit
+  __shared__ V2 slab[kLds ? 3 * A::N * kBlock : 1];
+  ABRK_ROW_INDEX
+  std::conditional_t<kLds, LdsScratch<T, A::N>, TabScratch<T, A::N>> scr;
+  if constexpr (kLds) {
+    scr.slab = slab;
+    scr.lane = (int)threadIdx.x;
+  }
+  scr.sctab = sctab;
+  plant_body<A, T>(b, arm, P, qg, dqg, ug, ddqg, scr);
+}
+
 template <class A, class T>
 __global__ void __launch_bounds__(kBlock, kMinWaves)
 ik_kernel(A arm, IkP<T> P, long B, const T* __restrict__ qg, const T* __restrict__ tg, T* __restrict__ pp,
@@ -633,6 +659,12 @@ struct RolloutArgs {
   void *ierr, *qt, *dqt, *ut;
 };
 
+struct PlantArgs {
+  const void* P;  // PlantP<T>
+  void *q, *dq;   // mode 1: advanced in place
+  const void* u;
+  void* ddq;      // mode 0: the output
+};
 struct LawArgs {
   const void* P;  // OscP<T>
   const void *J, *M, *g, *c, *xyz, *R, *q, *dq, *target, *tv, *une;
@@ -682,6 +714,7 @@ struct ArmOps {
   hipError_t (*ik)(int dtype, const LaunchArgs&, const IkArgs&);
   hipError_t (*floating)(int dtype, const LaunchArgs&, const FloatingArgs&);
   hipError_t (*obstacles)(int dtype, const LaunchArgs&, const ObstaclesArgs&);
+  hipError_t (*plant)(int dtype, const LaunchArgs&, const PlantArgs&);
 };
 hipError_t launch_twolink_step(int dtype, const LaunchArgs& la, const void* K, void* q, void* dq, const void* u);
 
@@ -837,6 +870,11 @@ struct Launch {
                        (const T*)a.tv, (T*)a.u);
     return hipGetLastError();
   }
+  static hipError_t plant(const LaunchArgs& la, const PlantArgs& a) {
+    hipLaunchKernelGGL((plant_kernel<A, T>), grid_for(la.B), dim3(kBlock), 0, la.stream, arm_of(la),
+                       *static_cast<const PlantP<T>*>(a.P), la.B, (T*)a.q, (T*)a.dq, (const T*)a.u, (T*)a.ddq);
+    return hipGetLastError();
+  }
 };
 
 // ops for an arm policy available in both arithmetic types (AD = double flavour, AF = float)
@@ -917,9 +955,12 @@ struct OpsFor {
   static hipError_t obstacles(int dt, const LaunchArgs& la, const ObstaclesArgs& a) {
     return dt == 0 ? obstacles_t<AD, double>(la, a) : obstacles_t<AF, float>(la, a);
   }
+  static hipError_t plant(int dt, const LaunchArgs& la, const PlantArgs& a) {
+    return dt == 0 ? Launch<AD, double>::plant(la, a) : Launch<AF, float>::plant(la, a);
+  }
   static const ArmOps* ops() {
     static const ArmOps o = {AD::N, &dyn, &osc, &sliding, &joint, AD::N == 2 ? &rollout : nullptr, &ik,
-                             &floating, &obstacles};
+                             &floating, &obstacles, &plant};
     return &o;
   }
 };

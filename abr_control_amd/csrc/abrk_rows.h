@@ -512,6 +512,35 @@ ABRK_INL void twolink_step_body(long b, const TwoLinkP<T>& K, T* __restrict__ qg
   store_row<2>(dqg, b, dq);
 }
 
+// ---- rigid-body plant of any arm (abrk_ctrl.h plant_row).  P.mode 0: forward dynamics - ddq leaves through `ddqg`,
+// q and dq are read only; P.mode 1: P.substeps Euler steps, q and dq written back in place (`ddqg` unused).
+template <class A, class T, class Scr>
+ABRK_INL void plant_body(long b, const A& arm, const PlantP<T>& P, T* __restrict__ qg, T* __restrict__ dqg,
+                         const T* __restrict__ ug, T* __restrict__ ddqg, Scr& scr) {
+  constexpr int N = A::N;
+  T q[N], dq[N], ddq[N];
+  load_row<N>(qg, b, q);
+  load_row<N>(dqg, b, dq);
+  // u is read where a substep consumes it, every substep (after the first from the cache): held in registers across the
+  // dynamics pass its N values push the six-joint fp64 kernel past the two-wave budget
+  auto get_u = [&](T(&u)[N]) ABRK_LAMBDA {
+    const T* up = ug;
+    opaque(up);
+    load_row<N>(up, b, u);
+  };
+  T minpiv = T(1);
+  const bool integrate = P.mode != 0;
+  plant_row<A, T>(arm, P.h, integrate ? P.substeps : 1, P.gravity != 0, integrate, q, dq, get_u, ddq, minpiv, scr);
+  if (integrate) {
+    store_row<N>(qg, b, q);
+    store_row<N>(dqg, b, dq);
+  } else {
+    store_row<N>(ddqg, b, ddq);
+  }
+  // ABRK_ESINGULAR (abrk_ctrl.h flag_singular), after the row's outputs
+  if (any_lane(!(minpiv > T(0))) && P.status) *P.status = 1;
+}
+
 // ---- OSC._Mx / ._velocity_limiting / ._calc_orientation_forces for B rows (osc.py:120-215)
 template <int N, class T>
 ABRK_INL void mx_body(long b, int k, T thr, const T* __restrict__ Mg, const T* __restrict__ Jg, T* __restrict__ Mxg,

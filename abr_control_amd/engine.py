@@ -551,6 +551,26 @@ def twolink_step(plant, q, dq, u, dtype=np.float64, device=0, stream=None):
     check(lib().abrk_twolink_step_batch(a.code, C.byref(plant), B, qp, dqp, up, device, _sp(stream)))
 
 
+def forward_dynamics(arm_id, n, q, dq, u, ddq=None, dtype=np.float64, device=0, stream=None):
+    """ddq = M(q)^-1 (u - C(q,dq) dq - g(q)) for B states: q, dq, u [B,n] -> ddq [B,n]."""
+    a = _Args(dtype)
+    B = q.shape[0]
+    qp, dqp, up = a.inp(q, (B, n), "q"), a.inp(dq, (B, n), "dq"), a.inp(u, (B, n), "u")
+    op, oo = a.out(ddq, (B, n), device, "ddq")
+    check(lib().abrk_forward_dynamics_batch(arm_id, a.code, B, qp, dqp, up, op, device, _sp(stream)))
+    return oo
+
+
+def plant_step(arm_id, n, params, q, dq, u, dtype=np.float64, device=0, stream=None):
+    """Rigid-body plant of any arm: (q, dq) [B,n] advanced in place by params.dt (_abi.make_plant_params) under the
+    torques u [B,n]."""
+    a = _Args(dtype)
+    B = q.shape[0]
+    qp, dqp = _inout(a, q, (B, n), "q"), _inout(a, dq, (B, n), "dq")
+    up = a.inp(u, (B, n), "u")
+    check(lib().abrk_plant_step_batch(arm_id, a.code, C.byref(params), B, qp, dqp, up, device, _sp(stream)))
+
+
 def osc_rollout_twolink(arm_id, params, plant, q, dq, target, n_steps, every=0, integrated_error=None,
                         want_traj=False, dtype=np.float64, device=0, stream=None):
     """n_steps x { OSC.generate ; ArmSim._step } in one launch.  q, dq [B,2] are advanced in place.

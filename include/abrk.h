@@ -331,6 +331,29 @@ int abrk_osc_rollout_twolink_batch(int arm_id, int dtype, const abrk_osc_params*
                                    void* q_traj, void* dq_traj, void* u_traj, int device, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Rigid-body plant of ANY arm: forward dynamics and Euler steps on the device, so that a recorded plan
+ * { control law; plant step } closes the loop without the host (abrk_plan_begin .. abrk_plan_end).
+ *   ddq = M(q)^-1 (u - C(q,dq) dq - g(q))      with M, C, g as robot_config.M / .C / .g return them
+ *   `substeps` times, h = dt / substeps, u held:  dq += ddq h;  q += dq h     (the update order of
+ *   abr_control/arms/twojoint/arm_sim.py:131-132; arms/threejoint/arm_sim.py:93-94 takes dt/1e-5 such substeps)
+ * gravity = 0 leaves g out.  No joint friction, joint limits or contacts.
+ * A row whose M has a non-positive Cholesky pivot is reported as ABRK_ESINGULAR exactly as by
+ * abrk_osc_generate_batch: host arrays - the call returns the code; device pointers - the stream's next sync does.
+ * --------------------------------------------------------------------------------- */
+typedef struct abrk_plant_params {
+  double dt;
+  int32_t substeps; /* >= 1 */
+  int32_t gravity;
+} abrk_plant_params;
+
+/* ddq [B,n] for B states (q, dq, u [B,n]); q, dq are not written.                                */
+int abrk_forward_dynamics_batch(int arm_id, int dtype, int64_t B, const void* q, const void* dq,
+                                const void* u, void* ddq, int device, void* stream);
+/* (q, dq) [B,n] advanced in place by params->dt under the torques u [B,n] (host arrays: staged in and out). */
+int abrk_plant_step_batch(int arm_id, int dtype, const abrk_plant_params* params, int64_t B,
+                          void* q, void* dq, const void* u, int device, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Iterative inverse kinematics: InverseKinematics.generate_path
  * (abr_control/controllers/path_planners/inverse_kinematics.py:28-135) for B independent paths, all
  * n_timesteps iterations of a path inside one kernel (each iteration: Tx, J, quaternion of the EE, two

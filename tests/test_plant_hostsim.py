@@ -1,0 +1,124 @@
+"""The plant row program (abrk_ctrl.h plant_row) built for the host (tests/hostsim_plant) against the oracle composed in
+NumPy: ddq = solve(M, u - C dq - g) per row and the plain loop of dq += ddq h, q += dq h.  32 rows per case, no row left
+out; bars: 1e-6 (fp64) and 1e-4 (fp32) on max|d| / max|ref| per row."""
+import json
+import os
+
+import numpy as np
+import pytest
+
+from abr_control_amd import _abi
+from tests import hostsim_plant
+from tests.plant_ref import TOL_F32, TOL_F64, OracleDyn, Ref, draw, rel_err
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+B = 32
+
+
+class HostsimGiDyn:
+    """M, C, g of a general-inertia table: the host build of the dynamics row program, which tests/test_general_inertia.py
+    pins to the reference's fixtures (the oracle library knows diagonal inertias only)"""
+
+    def __init__(self, table):
+        self.table = table
+
+    def mcg(self, q, dq):
+        from tests import hostsim_gi
+
+        r = hostsim_gi.dynamics(self.table, q[None], dq[None], want=("M", "g", "C"))
+        return r["M"][0], r["C"][0], r["g"][0]
+
+
+def _gi(name):
+    with open(os.path.join(GOLDEN, f"inertia_{name}.json")) as fh:
+        return json.load(fh)
+
+
+def _case(name):
+    """-> (table, runtime, reference)"""
+    if name.startswith("gi_"):
+        tab = _abi.normalize_table(_gi(name[3:]))
+        return tab, False, Ref(HostsimGiDyn(tab))
+    if name == "ur5_rt":
+        tab = _abi.load_table("ur5")
+        return tab, True, Ref(OracleDyn(tab))
+    tab = _abi.load_table(name)
+    return tab, False, Ref(OracleDyn(tab))
+
+
+CASES = ("onejoint", "twojoint", "threejoint", "ur5", "jaco2", "ur5_rt", "gi_synthetic4", "gi_ur5")
+
+
+@pytest.mark.parametrize("dtype", (np.float64, np.float32), ids=("f64", "f32"))
+@pytest.mark.parametrize("name", CASES)
+def test_plant_hostsim_ddq_and_one_step(name, dtype):
+    """Worst measured over all cases: fp64 ddq 2.0e-15, q / dq after a step 5.6e-16; fp32 ddq 1.1e-6 (gi_synthetic4),
+    q / dq after a step 3.1e-7."""
+    tab, rt, ref = _case(name)
+    n = int(tab["n_joints"])
+    q, dq, u = draw(11, B, n)
+    tol = TOL_F64 if dtype == np.float64 else TOL_F32
+    if name == "onejoint":
+        # the reference's one-joint arm carries no mass on its only link (arms/onejoint/config.py): M = [[0]], the
+        # reference value is numpy's LinAlgError, and the row program raises the flag the kernels report as ESINGULAR
+        with pytest.raises(np.linalg.LinAlgError):
+            ref.ddq(q, dq, u)
+        assert hostsim_plant.is_singular(tab, q, dq, u, dtype=dtype)
+        return
+    assert not hostsim_plant.is_singular(tab, q, dq, u, dtype=dtype, runtime=rt)
+    got = hostsim_plant.forward_dynamics(tab, q, dq, u, dtype=dtype, runtime=rt)
+    e = rel_err(got, ref.ddq(q, dq, u))
+    print(f"{name} {np.dtype(dtype).name} ddq {e:.2e}")
+    assert e <= tol
+    e0 = rel_err(hostsim_plant.forward_dynamics(tab, q, dq, u, dtype=dtype, runtime=rt, gravity=False),
+                 ref.ddq(q, dq, u, gravity=False))
+    assert e0 <= tol
+    for sub in (1, 4):
+        qg, dqg = hostsim_plant.plant_step(tab, 1e-3, sub, q, dq, u, dtype=dtype, runtime=rt)
+        qr, dqr = ref.steps(q, dq, u, 1e-3, sub)
+        eq, edq = rel_err(qg, qr), rel_err(dqg, dqr)
+        print(f"{name} {np.dtype(dtype).name} substeps {sub}: q {eq:.2e} dq {edq:.2e}")
+        assert eq <= tol and edq <= tol
+
+
+def test_plant_hostsim_gi_ddq_against_the_fixture():
+    """the general-inertia table whose fixture carries M, g AND C (synthetic4), at the fixture's own 12 states: the
+    reference's SymPy output composed in NumPy.  Worst measured: 5.0e-15."""
+    tab = _abi.normalize_table(_gi("synthetic4"))
+    z = np.load(os.path.join(GOLDEN, "inertia_synthetic4.npz"))
+    q, dq = z["dyn_q"], z["dyn_dq"]
+    u = draw(12, q.shape[0], q.shape[1])[2]
+    ref = np.stack([np.linalg.solve(z["M"][b], u[b] - z["C"][b] @ dq[b] - z["g"][b]) for b in range(q.shape[0])])
+    e = rel_err(hostsim_plant.forward_dynamics(tab, q, dq, u), ref)
+    print(f"gi synthetic4 vs fixture {e:.2e}")
+    assert e <= TOL_F64
+
+
+@pytest.mark.parametrize("name", ("ur5", "jaco2"))
+def test_plant_hostsim_fifty_steps(name):
+    """50 steps of 1 ms, one call each, against the NumPy loop.  Worst measured: ur5 3.9e-16, jaco2 5.6e-16."""
+    tab, rt, ref = _case(name)
+    q, dq, u = draw(13, B, int(tab["n_joints"]))
+    qg, dqg = q, dq
+    for _ in range(50):
+        qg, dqg = hostsim_plant.plant_step(tab, 1e-3, 1, qg, dqg, u)
+    qr, dqr = ref.steps(q, dq, u, 1e-3, 1, 50)
+    eq, edq = rel_err(qg, qr), rel_err(dqg, dqr)
+    print(f"{name} 50 steps: q {eq:.2e} dq {edq:.2e}")
+    assert eq <= TOL_F64 and edq <= TOL_F64
+
+
+@pytest.mark.parametrize("name", ("threejoint", "ur5", "jaco2", "ur5_rt"))
+def test_plant_hostsim_inverse_dynamics_identity(name):
+    """forward_dynamics(q, dq, M a + C dq + g) = a for random a.  Worst measured: 9.9e-15 (ur5)."""
+    tab, rt, ref = _case(name)
+    n = int(tab["n_joints"])
+    q, dq, _ = draw(14, B, n)
+    a = np.random.RandomState(15).uniform(-30, 30, (B, n))
+    u = np.empty_like(q)
+    for b in range(B):
+        M, Cm, g = ref.dyn(q[b], dq[b])
+        u[b] = M @ a[b] + Cm @ dq[b] + g
+    e = rel_err(hostsim_plant.forward_dynamics(tab, q, dq, u, runtime=rt), a)
+    print(f"{name} identity {e:.2e}")
+    assert e <= TOL_F64
