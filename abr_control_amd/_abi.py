@@ -26,8 +26,9 @@ WANT_T = 1 << 7
 WANT_TINV = 1 << 8
 WANT_QUAT = 1 << 9
 
-ERRORS = {-1: "EINVAL", -2: "ENODEV", -3: "ENOMEM", -4: "ENOARM", -5: "EFRAME", -6: "ESINGULAR"}
+ERRORS = {-1: "EINVAL", -2: "ENODEV", -3: "ENOMEM", -4: "ENOARM", -5: "EFRAME", -6: "ESINGULAR", -7: "EPATH"}
 ESINGULAR = -6
+EPATH = -7
 
 
 class ArmDesc(C.Structure):
@@ -203,6 +204,34 @@ def make_twolink_plant(L, M_LINKS, dt=0.001):
     p.K4 = 1 / 2.0 * M[2][0, 0] * Ls[1] * Ls[2]
     p.dt = dt
     return p
+
+
+class PathParams(C.Structure):
+    """abrk_path_params (include/abrk.h)"""
+    _fields_ = [("dt", C.c_double), ("n_samples", C.c_int32), ("n_candidates", C.c_int32), ("axes", C.c_int32),
+                ("width", C.c_int32), ("table_len", C.c_int64)]
+
+
+# the 24 Euler axis sequences as (firstaxis, parity, repetition, frame), the encoding of utils/transformations.py
+EULER_AXES = {
+    "sxyz": (0, 0, 0, 0), "sxyx": (0, 0, 1, 0), "sxzy": (0, 1, 0, 0), "sxzx": (0, 1, 1, 0), "syzx": (1, 0, 0, 0),
+    "syzy": (1, 0, 1, 0), "syxz": (1, 1, 0, 0), "syxy": (1, 1, 1, 0), "szxy": (2, 0, 0, 0), "szxz": (2, 0, 1, 0),
+    "szyx": (2, 1, 0, 0), "szyz": (2, 1, 1, 0), "rzyx": (0, 0, 0, 1), "rxyx": (0, 0, 1, 1), "ryzx": (0, 1, 0, 1),
+    "rxzx": (0, 1, 1, 1), "rxzy": (1, 0, 0, 1), "ryzy": (1, 0, 1, 1), "rzxy": (1, 1, 0, 1), "ryxy": (1, 1, 1, 1),
+    "ryxz": (2, 0, 0, 1), "rzxz": (2, 0, 1, 1), "rxyz": (2, 1, 0, 1), "rzyz": (2, 1, 1, 1),
+}
+
+
+def euler_axes_code(axes):
+    """`axes` (one of the 24 strings, or the tuple) as the int the path kernels decode:
+    firstaxis | parity << 2 | repetition << 3 | frame << 4"""
+    try:
+        t = EULER_AXES[axes.lower()]
+    except (AttributeError, KeyError):
+        t = tuple(int(v) for v in axes) if not isinstance(axes, str) else None
+        if t not in EULER_AXES.values():
+            raise ValueError(f"axes {axes!r} is none of the 24 Euler axis sequences") from None
+    return t[0] | t[1] << 2 | t[2] << 3 | t[3] << 4
 
 
 class PlantParams(C.Structure):

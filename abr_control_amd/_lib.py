@@ -98,6 +98,11 @@ def lib():
         L.abrk_forward_dynamics_batch.argtypes = [C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp]
         L.abrk_plant_step_batch.argtypes = [C.c_int, C.c_int, C.POINTER(_abi.PlantParams), _i64, _vp, _vp, _vp,
                                             C.c_int, _vp]
+        L.abrk_path_plan_batch.argtypes = [C.POINTER(_abi.PathParams), _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, C.c_int,
+                                           _vp]
+        L.abrk_path_fill_batch.argtypes = [C.POINTER(_abi.PathParams), _vp, _vp, _i64, C.c_int32] + [_vp] * 8 + [
+            C.c_int, _vp]
+        L.abrk_path_next_batch.argtypes = [C.c_int, _i64, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]
         L.abrk_osc_rollout_twolink_batch.argtypes = [
             C.c_int, C.c_int, C.POINTER(_abi.OSCParams), C.POINTER(_abi.TwoLinkPlant), _i64, C.c_int32, C.c_int32,
             _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]
@@ -139,9 +144,16 @@ class SingularMatrixError(AbrkError, np.linalg.LinAlgError):
     what the reference's `np.linalg.inv(M)` raises at controllers/osc.py:136 - so `except LinAlgError` keeps working."""
 
 
+class PathError(AbrkError, ValueError):
+    """ABRK_EPATH: a row of a planned batch has no path (start == target, no max_v candidate fits, fewer than two steps).
+    Also a ValueError - what the reference's PathPlanner.generate_path raises (path_planner.py:245)."""
+
+
 def check(rc):
     if rc == _abi.ESINGULAR:
         raise SingularMatrixError(rc, lib().abrk_last_error().decode())
+    if rc == _abi.EPATH:
+        raise PathError(rc, lib().abrk_last_error().decode())
     if rc < 0:
         raise AbrkError(rc, lib().abrk_last_error().decode())
     return rc

@@ -24,6 +24,7 @@
 #include "abrk_plugin.h"
 #include "abrk_kernels.h"
 #include "abrk_params.h"
+#include "abrk_path.h"
 
 namespace abrk {
 const ArmOps* ops_ur5();
@@ -325,7 +326,16 @@ struct StatusWord {
     *host = 0;
     return true;
   }
+  // the second int of the slot: "a row has no path" of the path planner's plan pass (ABRK_EPATH), same life cycle
+  volatile int* path_host() const { return host ? host + 1 : nullptr; }
+  int* path_dev() const { return dev ? dev + 1 : nullptr; }
+  bool take_path() {
+    if (!host || !host[1]) return false;
+    host[1] = 0;
+    return true;
+  }
 };
+enum { kStatusSingular = 1, kStatusPath = 2 };
 namespace {
 struct StatusPool {
   std::mutex mu;
@@ -349,7 +359,7 @@ struct StatusPool {
     }
     StatusWord w = free_.back();
     free_.pop_back();
-    *w.host = 0;
+    w.host[0] = w.host[1] = 0;
     handed_out++;
     return w;
   }
@@ -384,16 +394,21 @@ static StatusWord* status_word(bool synchronous, int device, void* stream = null
   if (!w.host) w = status_pool().get();
   return w.host ? &w : nullptr;
 }
-// was the flag of (device, stream) raised since it was last reported?  all_streams: any stream of the device
-static bool status_take(int device, void* stream, bool all_streams) {
+// which flags of (device, stream) were raised since they were last reported (kStatus* bits)?  all_streams: any stream
+// of the device
+static int status_take(int device, void* stream, bool all_streams) {
   std::lock_guard<std::mutex> lk(g_status_mu);
-  bool raised = false;
+  int raised = 0;
+  auto take = [&](StatusWord& w) {
+    if (w.take()) raised |= kStatusSingular;
+    if (w.take_path()) raised |= kStatusPath;
+  };
   if (all_streams) {
     for (auto it = g_stream_status.lower_bound({device, nullptr}); it != g_stream_status.end() && it->first.first == device; ++it)
-      raised = it->second.take() || raised;
+      take(it->second);
   } else {
     auto it = g_stream_status.find({device, stream});
-    if (it != g_stream_status.end()) raised = it->second.take();
+    if (it != g_stream_status.end()) take(it->second);
   }
   return raised;
 }
@@ -409,6 +424,13 @@ static int singular_error() {
                               "definite (numpy.linalg.inv(M) raises LinAlgError there, osc.py:136); the outputs of "
                               "those rows are unspecified");
 }
+static int path_error() {
+  return fail(ABRK_EPATH, "at least one row has no path: start == target, no max_v candidate whose ramps fit the curve "
+                          "(the reference raises ValueError at path_planner.py:245), or fewer than 2 / more than 2e9 "
+                          "steps; n_timesteps is 0 for those rows");
+}
+// what a drained stream reports: a singular batch first, else a row without a path
+static int status_error(int raised) { return (raised & kStatusSingular) ? singular_error() : path_error(); }
 
 extern "C" int abrk_device_count(void) {
   int n = 0;
@@ -454,7 +476,7 @@ extern "C" int abrk_memcpy_d2h(int device, void* dst, const void* src, size_t by
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   // the stream is drained: a singular batch enqueued on it earlier is reported here (the bytes ARE copied; the torques of
   // the offending rows are unspecified - a caller that reads results back this way must not get them silently)
-  if (status_take(device, stream, false)) return singular_error();
+  if (const int raised = status_take(device, stream, false)) return status_error(raised);
   return 0;
 }
 extern "C" int abrk_memset(int device, void* dst, int value, size_t bytes, void* stream) {
@@ -497,13 +519,13 @@ extern "C" int abrk_stream_sync(int device, void* stream) {
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   }
   // the "M not positive definite" flag of THIS stream's asynchronous (device-pointer) OSC calls: reported once
-  if (status_take(device, stream, false)) return singular_error();
+  if (const int raised = status_take(device, stream, false)) return status_error(raised);
   return 0;
 }
 extern "C" int abrk_device_sync(int device) {
   if (int rc = use_device(device)) return rc;
   HIPCHK(hipDeviceSynchronize());
-  if (status_take(device, nullptr, true)) return singular_error();  // every stream of the device is drained
+  if (const int raised = status_take(device, nullptr, true)) return status_error(raised);  // every stream is drained
   return 0;
 }
 extern "C" void* abrk_event_create(int device) {
@@ -2069,6 +2091,126 @@ extern "C" int abrk_plant_step_batch(int arm_id, int dtype, const abrk_plant_par
   if (!positive_finite_at(&P->dt)) return fail(ABRK_EINVAL, "dt=%g is not a positive finite step", P->dt);
   if (P->substeps < 1) return fail(ABRK_EINVAL, "substeps=%d < 1", P->substeps);
   return plant_impl(arm_id, dtype, 1, P->dt, P->substeps, P->gravity ? 1 : 0, B, q, dq, u, nullptr, device, stream);
+}
+
+// ------------------------------------------------------------------------------- path planner
+namespace {
+// the checks every path entry shares; -> PathArgs with the table fields set (the arrays are bound by the caller)
+int check_path(const abrk_path_params* P, const void* table, const int64_t* off, int64_t B, PathArgs* out) {
+  if (recording()) return fail(ABRK_EINVAL, "the path planning entry points cannot be recorded into a plan (abrk_path_next_batch can)");
+  if (!P || !table || !off) return fail(ABRK_EINVAL, "params, table and offsets are required");
+  if (B < 0 || B > 2147483647) return fail(ABRK_EINVAL, "batch %lld outside 0..2^31-1", (long long)B);
+  if (P->n_samples < 2) return fail(ABRK_EINVAL, "n_samples=%d < 2", P->n_samples);
+  if (P->n_candidates < 1 || P->n_candidates > 1 << 20) return fail(ABRK_EINVAL, "n_candidates=%d outside 1..2^20", P->n_candidates);
+  if (!positive_finite_at(&P->dt)) return fail(ABRK_EINVAL, "dt=%g is not a positive finite step", P->dt);
+  if (P->width != 6 && P->width != 12) return fail(ABRK_EINVAL, "width=%d is not 6 or 12", P->width);
+  if (P->axes < 0 || P->axes > 31 || (P->axes & 3) == 3) return fail(ABRK_EINVAL, "axes code %d is none of the 24 sequences", P->axes);
+  if (P->table_len < 0) return fail(ABRK_EINVAL, "negative table_len");
+  const int64_t len = P->table_len, S = P->n_samples, K = P->n_candidates;
+  auto inside = [&](int64_t o, int64_t n) { return o >= 0 && n >= 0 && o <= len && n <= len - o; };
+  if (!inside(off[0], 3 * S)) return fail(ABRK_EINVAL, "offsets[0]: the sample table leaves the packed table");
+  if (!inside(off[1], 3 * K)) return fail(ABRK_EINVAL, "offsets[1]: the candidate scalars leave the packed table");
+  for (int64_t k = 0; k < K; k++) {
+    const int64_t* o = off + 2 + 4 * k;
+    if (!inside(o[0], o[1]) || !inside(o[2], o[3]) || o[1] > 1000000000 || o[3] > 1000000000)
+      return fail(ABRK_EINVAL, "offsets: a ramp of candidate %lld leaves the packed table", (long long)k);
+  }
+  out->dt = P->dt;
+  out->S = (int)S;
+  out->K = (int)K;
+  out->axes = P->axes;
+  out->W = P->width;
+  out->B = (long)B;
+  return 0;
+}
+}  // namespace
+
+extern "C" int abrk_path_plan_batch(const abrk_path_params* P, const void* table, const int64_t* offsets, int64_t B,
+                                    const void* start, const void* target, void* n_timesteps, void* rowplan,
+                                    void* dist_steps, int device, void* stream) {
+  PathArgs pa{};
+  if (int rc = check_path(P, table, offsets, B, &pa)) return rc;
+  if (!start || !target || !n_timesteps || !rowplan || !dist_steps)
+    return fail(ABRK_EINVAL, "start, target, n_timesteps, rowplan and dist_steps are required");
+  if (B == 0) return 0;
+  if (int rc = use_device(device)) return rc;
+  Stager st{device, (hipStream_t)stream};
+  st.in((const void**)&pa.tab, table, (size_t)P->table_len * 8);
+  st.in((const void**)&pa.off, offsets, (size_t)(2 + 4 * (size_t)pa.K) * 8);
+  st.in((const void**)&pa.start, start, (size_t)B * 24);
+  st.in((const void**)&pa.target, target, (size_t)B * 24);
+  st.out((void**)&pa.n_timesteps, n_timesteps, (size_t)B * 4);
+  st.out((void**)&pa.rowplan, rowplan, (size_t)B * 8);
+  st.out((void**)&pa.dist_steps, dist_steps, (size_t)B * pa.S * 8);
+  if (int rc = st.reserve()) return rc;
+  // anything staged (as a rule the offsets, which live on the host): the call is synchronous and reports a row without
+  // a path itself, on the calling thread's word; device-visible memory throughout: the stream's next sync does
+  StatusWord* sw = status_word(st.staged, device, stream);
+  pa.status = sw ? sw->path_dev() : nullptr;
+  if (sw && st.staged) *sw->path_host() = 0;
+  HIPCHK(launch_path_plan(pa, (hipStream_t)stream));
+  if (int rc = st.finish()) return rc;
+  return st.staged && sw && sw->take_path() ? path_error() : 0;
+}
+
+extern "C" int abrk_path_fill_batch(const abrk_path_params* P, const void* table, const int64_t* offsets, int64_t B,
+                                    int32_t t_max, const void* start, const void* target,
+                                    const void* start_orientation, const void* target_orientation,
+                                    const void* n_timesteps, const void* rowplan, const void* dist_steps, void* path,
+                                    int device, void* stream) {
+  PathArgs pa{};
+  if (int rc = check_path(P, table, offsets, B, &pa)) return rc;
+  if (t_max < 1) return fail(ABRK_EINVAL, "t_max=%d < 1", t_max);
+  if (!start || !target || !n_timesteps || !rowplan || !dist_steps || !path)
+    return fail(ABRK_EINVAL, "start, target, n_timesteps, rowplan, dist_steps and path are required");
+  if (P->width == 12 && (!start_orientation || !target_orientation))
+    return fail(ABRK_EINVAL, "a 12-wide path needs start_orientation and target_orientation");
+  if (B == 0) return 0;
+  if (int rc = use_device(device)) return rc;
+  const bool ori = P->width == 12;
+  Stager st{device, (hipStream_t)stream};
+  st.in((const void**)&pa.tab, table, (size_t)P->table_len * 8);
+  st.in((const void**)&pa.off, offsets, (size_t)(2 + 4 * (size_t)pa.K) * 8);
+  st.in((const void**)&pa.start, start, (size_t)B * 24);
+  st.in((const void**)&pa.target, target, (size_t)B * 24);
+  st.in((const void**)&pa.start_o, ori ? start_orientation : nullptr, (size_t)B * 24);
+  st.in((const void**)&pa.target_o, ori ? target_orientation : nullptr, (size_t)B * 24);
+  st.in((const void**)&pa.n_timesteps, n_timesteps, (size_t)B * 4);
+  st.in((const void**)&pa.rowplan, rowplan, (size_t)B * 8);
+  st.in((const void**)&pa.dist_steps, dist_steps, (size_t)B * pa.S * 8);
+  st.out((void**)&pa.path, path, (size_t)B * t_max * P->width * 8);
+  if (int rc = st.reserve()) return rc;
+  pa.Tmax = t_max;
+  HIPCHK(launch_path_fill(pa, (hipStream_t)stream));
+  HIPCHK(launch_path_gradient(pa, (hipStream_t)stream));
+  return st.finish();
+}
+
+extern "C" int abrk_path_next_batch(int dtype, int64_t B, int32_t t_max, int32_t width, const void* path,
+                                    const void* n_timesteps, void* counter, void* target, void* target_velocity,
+                                    int device, void* stream) {
+  if (dtype != ABRK_F64 && dtype != ABRK_F32) return fail(ABRK_EINVAL, "dtype %d is not ABRK_F64/ABRK_F32", dtype);
+  if (B < 0) return fail(ABRK_EINVAL, "negative batch %lld", (long long)B);
+  if (t_max < 1) return fail(ABRK_EINVAL, "t_max=%d < 1", t_max);
+  if (width != 6 && width != 12) return fail(ABRK_EINVAL, "width=%d is not 6 or 12", width);
+  if (!path || !n_timesteps || !counter || !target) return fail(ABRK_EINVAL, "path, n_timesteps, counter and target are required");
+  if (B == 0) return 0;
+  if (int rc = use_device(device)) return rc;
+  const size_t s = esz(dtype);
+  Stager st{device, (hipStream_t)stream};
+  PathNextArgs na{};
+  st.in((const void**)&na.path, path, (size_t)B * t_max * width * 8);
+  st.in((const void**)&na.n_timesteps, n_timesteps, (size_t)B * 4);
+  st.inout((void**)&na.counter, counter, (size_t)B * 4);
+  // a 6-wide path leaves the orientation columns as they are: the arrays go in as well as out
+  st.inout(&na.target, target, (size_t)B * 6 * s);
+  st.inout(&na.target_velocity, target_velocity, (size_t)B * 6 * s);
+  if (int rc = st.reserve()) return rc;
+  na.B = (long)B;
+  na.Tmax = t_max;
+  na.W = width;
+  const hipStream_t hs = (hipStream_t)stream;
+  return dispatch(st, nullptr, dtype, [=](const void*) { return launch_path_next(dtype, na, hs); });
 }
 
 // ------------------------------------------------------------------------------- launch plans

@@ -591,6 +591,86 @@ def osc_rollout_twolink(arm_id, params, plant, q, dq, target, n_steps, every=0, 
     return outs if want_traj else None
 
 
+def _i32(arr, shape, name, device_mode):
+    """an int32 array argument of the path entries: DeviceArray or C-contiguous ndarray, passed as it is"""
+    if isinstance(arr, DeviceArray) != device_mode:
+        raise TypeError("mixing DeviceArray and NumPy arguments in one call is not supported")
+    if arr.dtype != np.int32 or tuple(arr.shape) != tuple(shape) or (not device_mode and not arr.flags.c_contiguous):
+        raise ValueError(f"{name}: expected a C-contiguous int32 array {tuple(shape)}, got {arr.dtype}{tuple(arr.shape)}")
+    return arr.ptr if device_mode else arr.ctypes.data
+
+
+def _path_table(a, params, table, offsets):
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    if offsets.shape != (2 + 4 * int(params.n_candidates),):
+        raise ValueError(f"offsets: expected {2 + 4 * int(params.n_candidates)} entries, got {offsets.shape}")
+    a.keep.append(offsets)
+    if isinstance(table, DeviceArray):  # (the table may live on the device while the rows come from the host)
+        if table.dtype != np.float64 or table.shape != (int(params.table_len),):
+            raise ValueError("table: expected a float64 DeviceArray of table_len values")
+        return table.ptr, offsets.ctypes.data
+    t = np.ascontiguousarray(table, dtype=np.float64)
+    if t.shape != (int(params.table_len),):
+        raise ValueError(f"table: expected {int(params.table_len)} values, got {t.shape}")
+    a.keep.append(t)
+    return t.ctypes.data, offsets.ctypes.data
+
+
+def path_plan(params, table, offsets, start, target, device=0, stream=None):
+    """The plan pass of the batched PathPlanner (abrk_path_plan_batch): start, target [B,3] ->
+    (n_timesteps [B] int32, rowplan [B,2] int32, dist_steps [B, n_samples]).  params: _abi.PathParams; table / offsets:
+    the packed profile tables (controllers/path_planners/path_planner.py builds them).  Raises PathError (a ValueError)
+    when a row has no path."""
+    a = _Args(np.float64)
+    B = start.shape[0]
+    sp, tp = a.inp(start, (B, 3), "start"), a.inp(target, (B, 3), "target")
+    tabp, offp = _path_table(a, params, table, offsets)
+    if a.on_device:
+        nt, rp = DeviceArray((B,), np.int32, device), DeviceArray((B, 2), np.int32, device)
+        ntp, rpp = nt.ptr, rp.ptr
+    else:
+        nt, rp = np.zeros((B,), np.int32), np.zeros((B, 2), np.int32)
+        ntp, rpp = nt.ctypes.data, rp.ctypes.data
+    dsp, ds = a.out(None, (B, int(params.n_samples)), device, "dist_steps")
+    check(lib().abrk_path_plan_batch(C.byref(params), tabp, offp, B, sp, tp, ntp, rpp, dsp, device, _sp(stream)))
+    return nt, rp, ds
+
+
+def path_fill(params, table, offsets, t_max, start, target, n_timesteps, rowplan, dist_steps, start_orientation=None,
+              target_orientation=None, path=None, device=0, stream=None):
+    """The fill and gradient passes (abrk_path_fill_batch) -> path [B, t_max, params.width]: row b is its path in
+    [:n_timesteps[b]] and its last point after that."""
+    a = _Args(np.float64)
+    B = start.shape[0]
+    sp, tp = a.inp(start, (B, 3), "start"), a.inp(target, (B, 3), "target")
+    sop, top = a.inp(start_orientation, (B, 3), "start_orientation"), a.inp(target_orientation, (B, 3), "target_orientation")
+    dsp = a.inp(dist_steps, (B, int(params.n_samples)), "dist_steps")
+    ntp, rpp = _i32(n_timesteps, (B,), "n_timesteps", a.on_device), _i32(rowplan, (B, 2), "rowplan", a.on_device)
+    tabp, offp = _path_table(a, params, table, offsets)
+    pp, po = a.out(path, (B, int(t_max), int(params.width)), device, "path")
+    check(lib().abrk_path_fill_batch(C.byref(params), tabp, offp, B, int(t_max), sp, tp, sop, top, ntp, rpp, dsp, pp,
+                                     device, _sp(stream)))
+    return po
+
+
+def path_next(path, n_timesteps, counter, target, target_velocity=None, dtype=np.float64, device=0, stream=None):
+    """PathPlanner.next() for B rows as a kernel (abrk_path_next_batch) - recordable into a Plan: target[b] =
+    path[b, counter[b], (0:3, 6:9)], target_velocity[b] = path[b, counter[b], (3:6, 9:12)], counter[b] advanced and
+    clamped to n_timesteps[b] - 1.  path: float64 [B, Tmax, 6 | 12]; target / target_velocity: [B,6] of `dtype`, updated in
+    place (a 6-wide path leaves their orientation columns alone); counter, n_timesteps: int32 [B]."""
+    a = _Args(dtype)
+    B, t_max, width = path.shape
+    dev = isinstance(path, DeviceArray)
+    a._mode(dev)
+    if path.dtype != np.float64 or (not dev and not path.flags.c_contiguous):
+        raise ValueError("path: expected a C-contiguous float64 array [B, Tmax, W]")
+    pp = path.ptr if dev else path.ctypes.data
+    ntp, cp = _i32(n_timesteps, (B,), "n_timesteps", dev), _i32(counter, (B,), "counter", dev)
+    tgp = _inout(a, target, (B, 6), "target")
+    tvp = None if target_velocity is None else _inout(a, target_velocity, (B, 6), "target_velocity")
+    check(lib().abrk_path_next_batch(a.code, B, int(t_max), int(width), pp, ntp, cp, tgp, tvp, device, _sp(stream)))
+
+
 class Plan:
     """One control tick recorded as a launch plan (abrk_plan_begin .. abrk_plan_end): every engine call made inside
     the `with` block - on DeviceArrays, with this plan's device and stream - is validated and converted once and its

@@ -372,6 +372,58 @@ int abrk_ik_generate_path_batch(int arm_id, int dtype, const abrk_ik_params* par
                                 const void* position, const void* target, void* position_path,
                                 void* velocity_path, int device, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * PathPlanner.generate_path (abr_control/controllers/path_planners/path_planner.py:99-452) for B independent
+ * movements, fp64 only: position profile warped onto start -> target, velocity-limited stepping along it, SLERP
+ * orientation (orientation.py:157-198, utils/transformations.py:1096-1147, 1333-1369, 1033-1093), np.gradient
+ * velocities.  What depends on the caller's profile OBJECTS is evaluated once per call by the caller (in this
+ * package: the Python classes' own step() / generate()) and handed over as ONE packed table of doubles plus an
+ * offsets array; what depends on a row runs on the device.
+ *   table   [table_len] doubles, host or device
+ *   offsets [2 + 4 n_candidates] int64, HOST-readable (validated against table_len on every call):
+ *     offsets[0]              S x 3 samples pos_profile.step(linspace(0, 1, S))            (path_planner.py:197-205)
+ *     offsets[1]              n_candidates x 3: max_v_k, starting_dist_k, ending_dist_k, for max_v_k = max_velocity
+ *                             - 0.1 k formed by repeated subtraction (:242-302; np.sum(profile * dt), :255, :269)
+ *     offsets[2 + 4k], [+1]   np.cumsum(starting_vel_profile_k * dt) and its length        (:249-251, :316)
+ *     offsets[2 + 4k + 2], [+3]  np.cumsum(ending_vel_profile_k * dt) and its length       (:257-265)
+ *   axes: firstaxis | parity << 2 | repetition << 3 | frame << 4 of transformations.py:1565-1590 ('rxyz' = 22,
+ *   'sxyz' = 0); width: 6 (position, velocity) or 12 (+ Euler angles, their np.gradient).
+ * Two calls, because the output is sized by the first one's result:
+ *   abrk_path_plan_batch: start, target [B,3] -> n_timesteps [B] int32 (0: the row has no path), rowplan [B,2] int32
+ *     (candidate taken, constant-speed steps), dist_steps [B, n_samples] doubles (cumulative chord lengths, :215).
+ *     A row without a path - start == target, every candidate rejected (the reference's ValueError, :245), fewer
+ *     than the 2 steps np.gradient needs - is reported as ABRK_EPATH the way ABRK_ESINGULAR is.
+ *   abrk_path_fill_batch: the same table and rows + the three arrays above -> path [B, t_max, width]; row b holds
+ *     its path in [:n_timesteps[b]] and its last point after that (what PathPlanner.next() keeps returning, :454-464).
+ *     t_max >= max(n_timesteps); rows with n_timesteps 0 are not written.  start_/target_orientation [B,3]: width 12.
+ * Neither can be recorded into a plan.
+ * --------------------------------------------------------------------------------- */
+typedef struct abrk_path_params {
+  double dt;            /* vel_profile.dt */
+  int32_t n_samples;    /* S >= 2 */
+  int32_t n_candidates; /* >= 1 */
+  int32_t axes;
+  int32_t width;
+  int64_t table_len;
+} abrk_path_params;
+
+int abrk_path_plan_batch(const abrk_path_params* params, const void* table, const int64_t* offsets, int64_t B,
+                         const void* start, const void* target, void* n_timesteps, void* rowplan, void* dist_steps,
+                         int device, void* stream);
+int abrk_path_fill_batch(const abrk_path_params* params, const void* table, const int64_t* offsets, int64_t B,
+                         int32_t t_max, const void* start, const void* target, const void* start_orientation,
+                         const void* target_orientation, const void* n_timesteps, const void* rowplan,
+                         const void* dist_steps, void* path, int device, void* stream);
+/* PathPlanner.next() (path_planner.py:454-464) for B rows, as the feed of a recorded loop: with n = counter[b]
+ * (clamped into the row's path), target[b] = path[b, n, (0:3, 6:9)], target_velocity[b] = path[b, n, (3:6, 9:12)]
+ * - the layout OSC.generate takes (osc.py:217-239) - and counter[b] = min(n + 1, n_timesteps[b] - 1).  A 6-wide path
+ * leaves the orientation columns of both outputs as they are.  path is fp64 [B, t_max, width]; `dtype` is the type of
+ * target / target_velocity [B,6] (NULL: not written): an fp32 loop is fed from the fp64 path.  counter, n_timesteps
+ * [B] int32.  Recordable: { path_next; OSC; plant step } replayed K times tracks K path points without the host. */
+int abrk_path_next_batch(int dtype, int64_t B, int32_t t_max, int32_t width, const void* path,
+                         const void* n_timesteps, void* counter, void* target, void* target_velocity, int device,
+                         void* stream);
+
 /* Joint.generate (controllers/joint.py:104-131) / Damping / RestingConfig standalone.
  *   ctrl.kind == ABRK_NULL_DAMPING: u = M (-kv dq)            (damping.py:31-32)
  *   ctrl.kind == ABRK_NULL_RESTING: RestingConfig.generate     (resting_config.py:33-42)

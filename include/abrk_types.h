@@ -21,6 +21,10 @@ enum {
   ABRK_ENOMEM = -3,   /* device allocation failed                                       */
   ABRK_ENOARM = -4,   /* unknown arm id / name                                          */
   ABRK_EFRAME = -5,   /* invalid frame id ("Invalid transformation name", ur5/config.py:337) */
+  ABRK_EPATH = -7,    /* the path planner's plan pass (abrk_path_plan_batch) met a row without a path: start == target, no
+                         max_v candidate whose ramps fit the curve (the reference raises ValueError,
+                         path_planners/path_planner.py:245), fewer than 2 steps.  n_timesteps is 0 for those rows; reported
+                         like ABRK_ESINGULAR (the call itself for host arrays, else the stream's next sync).        */
   ABRK_ESINGULAR = -6 /* a row's joint-space inertia matrix M is not positive definite: where the reference's
                          numpy.linalg.inv(M) raises LinAlgError (controllers/osc.py:136).  Host-array calls return
                          it themselves (the outputs of the offending rows are unspecified, every other row is

@@ -1,0 +1,59 @@
+"""Python side of the hostsim_path TEST AID (tests/hostsim_path/hostsim_path.cpp): the path planner's row programs
+built for the host on first use.  Never imported by the product."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+from abr_control_amd import _abi
+from abr_control_amd.controllers.path_planners.path_planner import profile_tables
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_CSRC = os.path.join(_HERE, "..", "..", "abr_control_amd", "csrc")
+_BUILD = os.path.join(_HERE, "build")
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is not None:
+        return _lib
+    srcs = [os.path.join(_HERE, "hostsim_path.cpp"), os.path.join(_CSRC, "abrk_path.h")]
+    os.makedirs(_BUILD, exist_ok=True)
+    so = os.path.join(_BUILD, "libhostsim_path.so")
+    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
+        tmp = f"{so}.{os.getpid()}.tmp"
+        r = subprocess.run(
+            ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O1", "-std=c++17", "-fPIC", "-shared",
+             "-fno-signed-zeros", "-ffinite-math-only", "--cuda-host-only", "-o", tmp, srcs[0]],
+            capture_output=True, text=True)
+        if r.returncode:
+            raise RuntimeError("hostsim_path build failed:\n" + r.stderr[-3000:])
+        os.replace(tmp, so)
+    L = C.CDLL(so)
+    head = [C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
+    L.hostsim_path_plan.argtypes = head + [C.c_void_p] * 5
+    L.hostsim_path_fill.argtypes = head + [C.c_int] + [C.c_void_p] * 8
+    _lib = L
+    return L
+
+
+def generate_path(pos_profile, vel_profile, start, target, max_velocity, start_orientation=None,
+                  target_orientation=None, start_velocity=0, target_velocity=0, axes="rxyz"):
+    """PathPlanner.generate_path for B rows on the host -> (path [B, Tmax, 6 | 12], n_timesteps [B]); n_timesteps is 0
+    (and the row zeros) where the row has no path"""
+    f8 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+    start, target, so, to = f8(start), f8(target), f8(start_orientation), f8(target_orientation)
+    B, W = start.shape[0], 6 if so is None else 12
+    table, off, cands = profile_tables(pos_profile, vel_profile, max_velocity, start_velocity, target_velocity)
+    S, K = int(pos_profile.n_sample_points), len(cands)
+    nt, rowplan, ds = np.zeros(B, np.int32), np.zeros((B, 2), np.int32), np.zeros((B, S))
+    p = lambda a: None if a is None else a.ctypes.data
+    head = (float(vel_profile.dt), S, K, _abi.euler_axes_code(axes), W, p(table), p(off), B)
+    L = lib()
+    L.hostsim_path_plan(*head, p(start), p(target), p(nt), p(rowplan), p(ds))
+    t_max = max(int(nt.max()), 1)
+    path = np.zeros((B, t_max, W))
+    L.hostsim_path_fill(*head, t_max, p(start), p(target), p(so), p(to), p(nt), p(rowplan), p(ds), p(path))
+    return path, nt
