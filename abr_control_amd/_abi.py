@@ -248,6 +248,52 @@ def make_plant_params(dt, substeps=1, gravity=True):
     return p
 
 
+class TraceParams(C.Structure):
+    """abrk_trace_params (include/abrk.h)"""
+    _fields_ = [("frame", C.c_int32), ("x_off", C.c_double * 3), ("every", C.c_int32), ("capacity", C.c_int32),
+                ("columns", C.c_uint32), ("tol", C.c_double)]
+
+
+# history columns of abrk_loop_trace_batch in their fixed order: name -> (ABRK_TR_* bit, width for n joints)
+TRACE_COLUMNS = {"q": (1 << 0, lambda n: n), "dq": (1 << 1, lambda n: n), "u": (1 << 2, lambda n: n),
+                 "target": (1 << 3, lambda n: 6), "xyz": (1 << 4, lambda n: 3), "err": (1 << 5, lambda n: 1)}
+
+
+def trace_columns_mask(columns):
+    """column names (any order, no repeats) -> the ABRK_TR_* mask"""
+    mask = 0
+    for c in columns:
+        if c not in TRACE_COLUMNS:
+            raise ValueError(f"unknown history column {c!r}: one of {tuple(TRACE_COLUMNS)}")
+        if mask & TRACE_COLUMNS[c][0]:
+            raise ValueError(f"history column {c!r} named twice")
+        mask |= TRACE_COLUMNS[c][0]
+    return mask
+
+
+def trace_layout(mask, n):
+    """-> ({name: (first column, width)} of the selected columns in history order, W)"""
+    out, o = {}, 0
+    for name, (bit, width) in TRACE_COLUMNS.items():
+        if mask & bit:
+            out[name] = (o, width(n))
+            o += width(n)
+    return out, o
+
+
+def make_trace_params(frame, x_off=None, every=1, capacity=0, columns=("xyz", "err"), tol=1e-3):
+    """Parameters of engine.loop_trace: `frame` as frame_id() numbers it, `columns` a tuple of names or a mask."""
+    p = TraceParams()
+    p.frame = int(frame)
+    for r in range(3):
+        p.x_off[r] = 0.0 if x_off is None else float(x_off[r])
+    p.every = int(every)
+    p.capacity = int(capacity)
+    p.columns = int(columns) if isinstance(columns, (int, np.integer)) else trace_columns_mask(columns)
+    p.tol = float(tol)
+    return p
+
+
 TABLE_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "arms", "tables")
 BUILTIN_ARMS = ("ur5", "jaco2", "twojoint", "threejoint", "onejoint")
 

@@ -103,6 +103,8 @@ def lib():
         L.abrk_path_fill_batch.argtypes = [C.POINTER(_abi.PathParams), _vp, _vp, _i64, C.c_int32] + [_vp] * 8 + [
             C.c_int, _vp]
         L.abrk_path_next_batch.argtypes = [C.c_int, _i64, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]
+        L.abrk_loop_trace_batch.argtypes = [C.c_int, C.c_int, C.POINTER(_abi.TraceParams), _i64] + [_vp] * 8 + [
+            C.c_int, _vp]
         L.abrk_osc_rollout_twolink_batch.argtypes = [
             C.c_int, C.c_int, C.POINTER(_abi.OSCParams), C.POINTER(_abi.TwoLinkPlant), _i64, C.c_int32, C.c_int32,
             _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]

@@ -2093,6 +2093,88 @@ extern "C" int abrk_plant_step_batch(int arm_id, int dtype, const abrk_plant_par
   return plant_impl(arm_id, dtype, 1, P->dt, P->substeps, P->gravity ? 1 : 0, B, q, dq, u, nullptr, device, stream);
 }
 
+// ------------------------------------------------------------------------------- loop recorder
+namespace {
+static_assert((unsigned)ABRK_TR_Q == (unsigned)TR_Q && (unsigned)ABRK_TR_DQ == (unsigned)TR_DQ &&
+                  (unsigned)ABRK_TR_U == (unsigned)TR_U && (unsigned)ABRK_TR_TARGET == (unsigned)TR_TARGET &&
+                  (unsigned)ABRK_TR_XYZ == (unsigned)TR_XYZ && (unsigned)ABRK_TR_ERR == (unsigned)TR_ERR,
+              "abrk_types.h and abrk_trace.h name the same columns");
+// Is the double at `p` finite?  On its bits, like positive_finite_at.
+__attribute__((noinline, optnone)) bool finite_at(const void* p) {
+  volatile uint64_t b;
+  memcpy(const_cast<uint64_t*>(&b), p, sizeof(uint64_t));
+  const uint64_t v = b;
+  return ((v >> 52) & 0x7ff) != 0x7ff;
+}
+template <class T>
+TraceP<T> make_tracep(const abrk_trace_params& P, int n) {
+  TraceP<T> p;
+  p.frame = P.frame;
+  for (int r = 0; r < 3; r++) p.off[r] = T(P.x_off[r]);
+  p.every = P.every;
+  p.capacity = P.capacity;
+  p.columns = P.columns;
+  p.W = trace_width(P.columns, n);
+  p.lds = 1;
+  p.tol = P.tol;
+  return p;
+}
+}  // namespace
+
+extern "C" int abrk_loop_trace_batch(int arm_id, int dtype, const abrk_trace_params* P, int64_t B, const void* q,
+                                     const void* dq, const void* u, const void* target, void* counter, void* history,
+                                     void* stats, void* settle, int device, void* stream) {
+  ArmEntry* a;
+  if (int rc = check_common(arm_id, dtype, B, &a)) return rc;
+  if (!a->ops->trace) return fail(ABRK_EINVAL, "this arm's kernels carry no loop recorder (rebuild its plugin)");
+  if (!P) return fail(ABRK_EINVAL, "params is NULL");
+  const int n = a->desc.n_joints;
+  if (P->frame < 0 || P->frame > 2 * n + 1) return fail(ABRK_EINVAL, "Invalid transformation name: frame id %d", P->frame);
+  for (int r = 0; r < 3; r++)
+    if (!finite_at(&P->x_off[r])) return fail(ABRK_EINVAL, "x_off[%d] is not finite", r);
+  if (!finite_at(&P->tol)) return fail(ABRK_EINVAL, "tol is not finite");
+  if (P->every < 1) return fail(ABRK_EINVAL, "every=%d < 1", P->every);
+  if (!history && !stats) return fail(ABRK_EINVAL, "neither a history nor statistics requested");
+  const unsigned cols = history ? P->columns : 0u;
+  if (history) {
+    if (P->capacity < 1) return fail(ABRK_EINVAL, "capacity=%d < 1", P->capacity);
+    if (!cols || (cols & ~(unsigned)TR_ALL)) return fail(ABRK_EINVAL, "column mask 0x%x is empty or has unknown bits", cols);
+  }
+  if (!counter) return fail(ABRK_EINVAL, "counter is NULL");
+  const bool need_err = (cols & ABRK_TR_ERR) || stats;
+  if (!q && (need_err || (cols & (ABRK_TR_Q | ABRK_TR_XYZ)))) return fail(ABRK_EINVAL, "q is NULL");
+  if (!dq && (cols & ABRK_TR_DQ)) return fail(ABRK_EINVAL, "the dq column is selected but dq is NULL");
+  if (!u && (cols & ABRK_TR_U)) return fail(ABRK_EINVAL, "the u column is selected but u is NULL");
+  if (!target && (need_err || (cols & ABRK_TR_TARGET))) return fail(ABRK_EINVAL, "err, the target column and the statistics need target");
+  if (stats && !settle) return fail(ABRK_EINVAL, "statistics need settle");
+  if (B == 0) return 0;
+  if (int rc = use_device(device)) return rc;
+  const size_t s = esz(dtype);
+  const int W = trace_width(cols, n);
+  Stager st{device, (hipStream_t)stream};
+  TraceArgs ta{};
+  st.in(&ta.q, q, (size_t)B * n * s);
+  st.in(&ta.dq, (cols & ABRK_TR_DQ) ? dq : nullptr, (size_t)B * n * s);
+  st.in(&ta.u, (cols & ABRK_TR_U) ? u : nullptr, (size_t)B * n * s);
+  st.in(&ta.target, target, (size_t)B * 6 * s);
+  st.inout(&ta.counter, counter, (size_t)B * 4);
+  // (in as well as out: slots that are not due keep the caller's values)
+  st.inout(&ta.history, history, history ? (size_t)P->capacity * B * W * s : 0);
+  st.inout(&ta.stats, stats, (size_t)B * 4 * 8);
+  st.inout(&ta.settle, stats ? settle : nullptr, (size_t)B * 4);
+  if (int rc = st.reserve()) return rc;
+  abrk_trace_params Pc = *P;
+  Pc.columns = cols;
+  auto pb = blocks([&](auto t) { return make_tracep<decltype(t)>(Pc, n); });
+  const ArmOps* ops = a->ops;
+  const hipStream_t hs = (hipStream_t)stream;
+  return dispatch(st, a, dtype, [=](const void* rt) {
+    TraceArgs o = ta;
+    o.P = pb.of(dtype);
+    return ops->trace(dtype, LaunchArgs{rt, (long)B, hs}, o);
+  });
+}
+
 // ------------------------------------------------------------------------------- path planner
 namespace {
 // the checks every path entry shares; -> PathArgs with the table fields set (the arrays are bound by the caller)

@@ -6,6 +6,7 @@
 
 #include "abrk_osc6_plan.h"
 #include "abrk_rows.h"
+#include "abrk_trace.h"
 
 namespace abrk {
 
@@ -488,6 +489,57 @@ plant_kernel(A arm, PlantP<T> P, long B, T* __restrict__ qg, T* __restrict__ dqg
   plant_body<A, T>(b, arm, P, qg, dqg, ug, ddqg, scr);
 }
 
+// The loop recorder (abrk_trace.h trace_body): forward kinematics only, so two waves per SIMD without scratch.
+// History rows of a wavefront whose rows share one slot - every wavefront, until a caller restarts some rows on their
+// own - are parked in LDS laid out like the slot's 64-row block of the history and streamed out linearly: 16 bytes per
+// lane and store where the block starts on a 16-byte boundary, one element per lane otherwise (B * W odd: every other
+// slot), either way contiguous across the wavefront.  Rows with different slots take the row-per-lane stores.
+template <class T>
+struct TraceLds {
+  T* buf;
+  long row0;
+  int lane;
+  bool lds;
+  template <class Emit>
+  __device__ __forceinline__ void put(T* __restrict__ hist, bool due, int slot, long b, bool active, long B, int W,
+                                      Emit&& emit) {
+    // (all 64 lanes arrive here; lane 0 is a row of the batch)
+    const int slot0 = __builtin_amdgcn_readfirstlane(slot), due0 = __builtin_amdgcn_readfirstlane((int)due);
+    if (!lds || !__all(!active || (slot == slot0 && (int)due == due0))) {
+      TraceDirect<T>{}.put(hist, due, slot, b, active, B, W, emit);
+      return;
+    }
+    if (!due0) return;
+    if (active) emit([&](int o, T v) ABRK_LAMBDA { buf[lane * W + o] = v; });
+    __syncthreads();
+    const long left = B - row0;
+    const int total = (int)(left < kBlock ? left : (long)kBlock) * W;  // elements of this block
+    T* o = hist + ((long)slot0 * B + row0) * W;
+    constexpr int V = 16 / sizeof(T);
+    if ((reinterpret_cast<unsigned long long>(o) & 15ull) == 0) {
+      using vec = T __attribute__((ext_vector_type(V)));
+      for (int e = lane * V; e < total; e += kBlock * V) {
+        if (e + V <= total) {
+          *reinterpret_cast<vec*>(o + e) = *reinterpret_cast<const vec*>(buf + e);
+        } else {
+          for (int c = e; c < total; c++) o[c] = buf[c];
+        }
+      }
+    } else {
+      for (int e = lane; e < total; e += kBlock) o[e] = buf[e];
+    }
+  }
+};
+template <class A, class T>
+__global__ void __launch_bounds__(kBlock, 2)
+trace_kernel(A arm, TraceP<T> P, long B, TraceIO<T> io) {
+  __shared__ __attribute__((aligned(16))) T slab[kBlock * trace_width(TR_ALL, A::N)];
+  const long row0 = (long)blockIdx.x * kBlock;
+  const long b = row0 + threadIdx.x;
+  TraceLds<T> st{slab, row0, (int)threadIdx.x, P.lds != 0};
+  trace_body<A, T>(b, b < B, st, arm, P, B, io);
+}
+
 template <class A, class T>
 __global__ void __launch_bounds__(kBlock, kMinWaves)
 ik_kernel(A arm, IkP<T> P, long B, const T* __restrict__ qg, const T* __restrict__ tg, T* __restrict__ pp,
@@ -665,6 +717,11 @@ struct PlantArgs {
   const void* u;
   void* ddq;      // mode 0: the output
 };
+struct TraceArgs {
+  const void* P;  // TraceP<T>
+  const void *q, *dq, *u, *target;
+  void *counter, *history, *stats, *settle;
+};
 struct LawArgs {
   const void* P;  // OscP<T>
   const void *J, *M, *g, *c, *xyz, *R, *q, *dq, *target, *tv, *une;
@@ -715,6 +772,7 @@ struct ArmOps {
   hipError_t (*floating)(int dtype, const LaunchArgs&, const FloatingArgs&);
   hipError_t (*obstacles)(int dtype, const LaunchArgs&, const ObstaclesArgs&);
   hipError_t (*plant)(int dtype, const LaunchArgs&, const PlantArgs&);
+  hipError_t (*trace)(int dtype, const LaunchArgs&, const TraceArgs&);
 };
 hipError_t launch_twolink_step(int dtype, const LaunchArgs& la, const void* K, void* q, void* dq, const void* u);
 
@@ -875,6 +933,16 @@ struct Launch {
                        *static_cast<const PlantP<T>*>(a.P), la.B, (T*)a.q, (T*)a.dq, (const T*)a.u, (T*)a.ddq);
     return hipGetLastError();
   }
+  static hipError_t trace(const LaunchArgs& la, const TraceArgs& a) {
+    // measurement switch: the row-per-lane history stores for every wavefront (profiles/loop_trace.md)
+    static const bool plain = measurement_env("ABRK_TRACE_PLAIN") != nullptr;
+    TraceP<T> P = *static_cast<const TraceP<T>*>(a.P);
+    P.lds = plain ? 0 : 1;
+    const TraceIO<T> io{(const T*)a.q, (const T*)a.dq, (const T*)a.u, (const T*)a.target, (int*)a.counter,
+                        (T*)a.history, (double*)a.stats, (int*)a.settle};
+    hipLaunchKernelGGL((trace_kernel<A, T>), grid_for(la.B), dim3(kBlock), 0, la.stream, arm_of(la), P, la.B, io);
+    return hipGetLastError();
+  }
 };
 
 // ops for an arm policy available in both arithmetic types (AD = double flavour, AF = float)
@@ -958,9 +1026,12 @@ struct OpsFor {
   static hipError_t plant(int dt, const LaunchArgs& la, const PlantArgs& a) {
     return dt == 0 ? Launch<AD, double>::plant(la, a) : Launch<AF, float>::plant(la, a);
   }
+  static hipError_t trace(int dt, const LaunchArgs& la, const TraceArgs& a) {
+    return dt == 0 ? Launch<AD, double>::trace(la, a) : Launch<AF, float>::trace(la, a);
+  }
   static const ArmOps* ops() {
     static const ArmOps o = {AD::N, &dyn, &osc, &sliding, &joint, AD::N == 2 ? &rollout : nullptr, &ik,
-                             &floating, &obstacles, &plant};
+                             &floating, &obstacles, &plant, &trace};
     return &o;
   }
 };

@@ -671,6 +671,40 @@ def path_next(path, n_timesteps, counter, target, target_velocity=None, dtype=np
     check(lib().abrk_path_next_batch(a.code, B, int(t_max), int(width), pp, ntp, cp, tgp, tvp, device, _sp(stream)))
 
 
+def loop_trace(arm_id, n, params, q, dq, u, target, counter, history=None, stats=None, settle=None, dtype=np.float64,
+               device=0, stream=None):
+    """One tick of the loop recorder (abrk_loop_trace_batch) - recordable into a Plan.  With t = counter[b]: xyz =
+    Tx(params.frame, params.x_off) of q[b], err = |target[b, :3] - xyz|; if t is a multiple of params.every and its slot
+    t / every < params.capacity, the selected columns go to history[slot, b, :]; stats[b] = (err_last, err_max, err_min,
+    err_sumsq) and settle[b] are updated; counter[b] = t + 1.  params: _abi.make_trace_params.  q, dq, u [B,n], target [B,6]
+    of `dtype` (None where no selected output needs one); counter, settle: int32 [B]; history: [capacity, B, W] of `dtype`;
+    stats: float64 [B,4].  counter, history, stats and settle are updated in place."""
+    a = _Args(dtype)
+    src = next((x for x in (q, target, dq, u) if x is not None), None)
+    if src is None:
+        raise ValueError("loop_trace needs at least one of q, dq, u, target")
+    B = src.shape[0]
+    dev = isinstance(src, DeviceArray)
+    qp, dqp, up = a.inp(q, (B, n), "q"), a.inp(dq, (B, n), "dq"), a.inp(u, (B, n), "u")
+    tp = a.inp(target, (B, 6), "target")
+    a._mode(dev)
+    cp = _i32(counter, (B,), "counter", dev)
+    hp = sp = sep = None
+    if history is not None:
+        W = _abi.trace_layout(int(params.columns), n)[1]
+        hp = _inout(a, history, (int(params.capacity), B, W), "history")
+    if stats is not None:
+        if isinstance(stats, DeviceArray) != dev:
+            raise TypeError("mixing DeviceArray and NumPy arguments in one call is not supported")
+        if stats.dtype != np.float64 or tuple(stats.shape) != (B, 4) or (not dev and not stats.flags.c_contiguous):
+            raise ValueError(f"stats: expected a C-contiguous float64 array {(B, 4)}, got {stats.dtype}{tuple(stats.shape)}")
+        sp = stats.ptr if dev else stats.ctypes.data
+    if settle is not None:
+        sep = _i32(settle, (B,), "settle", dev)
+    check(lib().abrk_loop_trace_batch(arm_id, a.code, C.byref(params), B, qp, dqp, up, tp, cp, hp, sp, sep, device,
+                                      _sp(stream)))
+
+
 class Plan:
     """One control tick recorded as a launch plan (abrk_plan_begin .. abrk_plan_end): every engine call made inside
     the `with` block - on DeviceArrays, with this plan's device and stream - is validated and converted once and its

@@ -424,6 +424,39 @@ int abrk_path_next_batch(int dtype, int64_t B, int32_t t_max, int32_t width, con
                          const void* n_timesteps, void* counter, void* target, void* target_velocity, int device,
                          void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * The output side of a recorded loop: what every closed-loop example of the reference keeps in ee_track / target_track /
+ * q_track lists and reduces with np.linalg.norm(ee - target), kept on the device.  One call = one tick of every row.  With
+ * t = counter[b]:
+ *   xyz = Tx(frame, x_off) of q[b] (as abrk_dynamics_batch);  err = |target[b, 0:3] - xyz| in `dtype`
+ *   history (may be NULL): if t % every == 0 and slot = t / every < capacity, the selected columns go to history[slot, b, :].
+ *     Columns (ABRK_TR_*, abrk_types.h) keep the order q, dq, u [n], target [6], xyz [3], err [1]; W = the sum of the selected
+ *     widths.  [capacity, B, W] of `dtype`, time-major: a tick's rows are contiguous.  Slots past `capacity` are dropped (no
+ *     ring buffer); slots never written keep what the caller filled them with.
+ *   stats (may be NULL) [B,4] ALWAYS fp64: err_last, err_max, err_min, err_sumsq - assigned at t == 0, combined after it
+ *     (max, min, += err^2).  settle [B] int32 (required with stats): err <= tol ? (settle ? settle : t + 1) : 0, i.e. 0 =
+ *     outside the tolerance now, k > 0 = inside since tick k - 1.
+ *   counter[b] = t + 1.  The tick is per row and lives in device memory (a graph replay repeats identical arguments): zero
+ *     filling counter, settle and stats - of all rows or of some - restarts them.
+ * q is read for xyz, err, stats and its own column; dq / u only for their columns; target for err, stats and its column: a
+ * source nothing selected needs may be NULL.  Goes through the staging of every *_batch call (host arrays work for one-off
+ * calls) and is recorded between abrk_plan_begin and abrk_plan_end: { path_next; law; plant step; loop_trace } replayed K
+ * times returns K ticks of trajectory and statistics with no host round trip.
+ * ABRK_EINVAL: dtype, B < 0, every < 1, a history with capacity < 1 or with an empty / unknown column mask, a NULL array
+ * that is needed, neither history nor stats, a frame id outside 0..2n+1, a non-finite tol or x_off.
+ * --------------------------------------------------------------------------------- */
+typedef struct abrk_trace_params {
+  int32_t frame;    /* link_i -> 2i, joint_i -> 2i+1, EE -> 2n+1 */
+  double x_off[3];
+  int32_t every;    /* >= 1: history keeps every `every`-th tick (statistics see every tick) */
+  int32_t capacity; /* history slots */
+  uint32_t columns; /* ABRK_TR_* */
+  double tol;
+} abrk_trace_params;
+int abrk_loop_trace_batch(int arm_id, int dtype, const abrk_trace_params* params, int64_t B, const void* q,
+                          const void* dq, const void* u, const void* target, void* counter, void* history, void* stats,
+                          void* settle, int device, void* stream);
+
 /* Joint.generate (controllers/joint.py:104-131) / Damping / RestingConfig standalone.
  *   ctrl.kind == ABRK_NULL_DAMPING: u = M (-kv dq)            (damping.py:31-32)
  *   ctrl.kind == ABRK_NULL_RESTING: RestingConfig.generate     (resting_config.py:33-42)

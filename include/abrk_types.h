@@ -41,6 +41,17 @@ enum {
                          inverts a float32 M too, osc.py:136 - returns finite values of no accuracy.               */
 };
 
+/* History columns of abrk_loop_trace_batch (abrk.h), in the order they take in a history row: q, dq, u [n],
+ * target [6], xyz [3], err [1]. */
+enum {
+  ABRK_TR_Q = 1u << 0,
+  ABRK_TR_DQ = 1u << 1,
+  ABRK_TR_U = 1u << 2,
+  ABRK_TR_TARGET = 1u << 3,
+  ABRK_TR_XYZ = 1u << 4,
+  ABRK_TR_ERR = 1u << 5
+};
+
 /* ---------------------------------------------------------------------------------
  * Arm description = the constant table a reference `Config.__init__` + `_calc_T`
  * encode symbolically (abr_control/arms/ur5/config.py:35-339, jaco2/config.py:35-356,
