@@ -147,7 +147,8 @@ class SingularMatrixError(AbrkError, np.linalg.LinAlgError):
 
 
 class PathError(AbrkError, ValueError):
-    """ABRK_EPATH: a row of a planned batch has no path (start == target, no max_v candidate fits, fewer than two steps).
+    """ABRK_EPATH: a row of a planned batch has no path (start == target, a movement exactly towards -(1,1,1)/sqrt(3),
+    no max_v candidate fits, fewer than two steps).
     Also a ValueError - what the reference's PathPlanner.generate_path raises (path_planner.py:245)."""
 
 

@@ -73,7 +73,9 @@ struct PathRow {
   double start[3];
 };
 
-// path_planner.py:184-192.  false: start == target (the reference divides by zero there)
+// path_planner.py:184-192.  false: start == target (the reference divides by zero there), or a movement exactly
+// towards -(1,1,1)/sqrt(3), where align_vectors divides by 1 + cs = 0 (the reference raises from generate_path).  The
+// library is built with -ffinite-math-only, so 1 + cs itself is tested, not the h it would give.
 ABRK_PATH_INL bool path_row_setup(const double* sp, const double* tp, PathRow& r) {
   double d[3];
   for (int c = 0; c < 3; c++) {
@@ -95,6 +97,7 @@ ABRK_PATH_INL bool path_row_setup(const double* sp, const double* tp, PathRow& r
   }
   const double v1 = a[1] * b[2] - a[2] * b[1], v2 = a[2] * b[0] - a[0] * b[2], v3 = a[0] * b[1] - a[1] * b[0];
   const double cs = a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
+  if (!(1.0 + cs > 0.0)) return false;
   const double h = 1.0 / (1.0 + cs);
   const double V[9] = {0.0, -v3, v2, v3, 0.0, -v1, -v2, v1, 0.0};
   for (int i = 0; i < 3; i++)

@@ -35,7 +35,7 @@ __global__ void __launch_bounds__(kPathBlock) path_fill_kernel(PathArgs a) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const long b = blockIdx.x;
   const int T = a.n_timesteps[b];
-  if (T < 2) return;  // (uniform over the workgroup)
+  if (T < 2 || T > a.Tmax) return;  // (uniform over the workgroup)  T > Tmax: the gradient pass skips the row as well
   {  // a rowplan that is not the plan pass's own for this table would index past the ramps: such a row is left alone
     const int k = a.rowplan[2 * b], c = a.rowplan[2 * b + 1];
     if (k < 0 || k >= a.K || c < 0 || a.off[2 + 4 * k + 1] + c + a.off[2 + 4 * k + 3] != T) return;
@@ -49,8 +49,7 @@ __global__ void __launch_bounds__(kPathBlock) path_fill_kernel(PathArgs a) {
   PathFillRow f;
   path_fill_setup(a, b, T, ds, f);
   double* row = a.path + b * (long)a.Tmax * a.W;
-  const int n = T < a.Tmax ? T : a.Tmax;
-  for (int i = threadIdx.x; i < n; i += kPathBlock) {
+  for (int i = threadIdx.x; i < T; i += kPathBlock) {
     double out[12];
     path_fill_step(a, f, ds, i, out);
     double* o = row + (long)i * a.W;

@@ -639,7 +639,8 @@ def path_plan(params, table, offsets, start, target, device=0, stream=None):
 def path_fill(params, table, offsets, t_max, start, target, n_timesteps, rowplan, dist_steps, start_orientation=None,
               target_orientation=None, path=None, device=0, stream=None):
     """The fill and gradient passes (abrk_path_fill_batch) -> path [B, t_max, params.width]: row b is its path in
-    [:n_timesteps[b]] and its last point after that."""
+    [:n_timesteps[b]] and its last point after that.  A row with n_timesteps[b] == 0 or n_timesteps[b] > t_max is left
+    as it was in every column: a path is never truncated."""
     a = _Args(np.float64)
     B = start.shape[0]
     sp, tp = a.inp(start, (B, 3), "start"), a.inp(target, (B, 3), "target")

@@ -391,11 +391,14 @@ int abrk_ik_generate_path_batch(int arm_id, int dtype, const abrk_ik_params* par
  * Two calls, because the output is sized by the first one's result:
  *   abrk_path_plan_batch: start, target [B,3] -> n_timesteps [B] int32 (0: the row has no path), rowplan [B,2] int32
  *     (candidate taken, constant-speed steps), dist_steps [B, n_samples] doubles (cumulative chord lengths, :215).
- *     A row without a path - start == target, every candidate rejected (the reference's ValueError, :245), fewer
- *     than the 2 steps np.gradient needs - is reported as ABRK_EPATH the way ABRK_ESINGULAR is.
+ *     A row without a path - start == target, a movement exactly towards -(1,1,1)/sqrt(3) (align_vectors, :75-97,
+ *     divides by zero there), every candidate rejected (the reference's ValueError, :245), fewer than the 2 steps
+ *     np.gradient needs - is reported as ABRK_EPATH the way ABRK_ESINGULAR is.
  *   abrk_path_fill_batch: the same table and rows + the three arrays above -> path [B, t_max, width]; row b holds
  *     its path in [:n_timesteps[b]] and its last point after that (what PathPlanner.next() keeps returning, :454-464).
- *     t_max >= max(n_timesteps); rows with n_timesteps 0 are not written.  start_/target_orientation [B,3]: width 12.
+ *     t_max >= max(n_timesteps) for all of it; a row with n_timesteps 0 or n_timesteps > t_max is not written at all
+ *     (no column of it, no truncated path; `path` is an output only, so into a HOST array such a row comes back
+ *     unspecified - a device array keeps what it held).  start_/target_orientation [B,3]: width 12.
  * Neither can be recorded into a plan.
  * --------------------------------------------------------------------------------- */
 typedef struct abrk_path_params {

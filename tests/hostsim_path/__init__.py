@@ -43,6 +43,14 @@ def generate_path(pos_profile, vel_profile, start, target, max_velocity, start_o
                   target_orientation=None, start_velocity=0, target_velocity=0, axes="rxyz"):
     """PathPlanner.generate_path for B rows on the host -> (path [B, Tmax, 6 | 12], n_timesteps [B]); n_timesteps is 0
     (and the row zeros) where the row has no path"""
+    return fill(pos_profile, vel_profile, start, target, start_orientation, target_orientation, None, 0.0, max_velocity,
+                start_velocity, target_velocity, axes, with_counts=True)
+
+
+def fill(pos_profile, vel_profile, start, target, start_orientation, target_orientation, t_max, sentinel, max_velocity,
+         start_velocity=0, target_velocity=0, axes="rxyz", with_counts=False):
+    """the plan pass, then the fill and gradient passes into a [B, t_max, 6 | 12] array that held `sentinel` everywhere
+    (t_max None: the largest step count) -> path, or (path, n_timesteps)"""
     f8 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
     start, target, so, to = f8(start), f8(target), f8(start_orientation), f8(target_orientation)
     B, W = start.shape[0], 6 if so is None else 12
@@ -53,7 +61,8 @@ def generate_path(pos_profile, vel_profile, start, target, max_velocity, start_o
     head = (float(vel_profile.dt), S, K, _abi.euler_axes_code(axes), W, p(table), p(off), B)
     L = lib()
     L.hostsim_path_plan(*head, p(start), p(target), p(nt), p(rowplan), p(ds))
-    t_max = max(int(nt.max()), 1)
-    path = np.zeros((B, t_max, W))
+    if t_max is None:
+        t_max = max(int(nt.max()), 1)
+    path = np.full((B, t_max, W), float(sentinel))
     L.hostsim_path_fill(*head, t_max, p(start), p(target), p(so), p(to), p(nt), p(rowplan), p(ds), p(path))
-    return path, nt
+    return (path, nt) if with_counts else path

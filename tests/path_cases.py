@@ -1,11 +1,13 @@
-"""The path planner's fixture cases (tests/golden/paths.{npz,json}, written by tools/gen_path_golden.py from the
-reference's own PathPlanner), loaded once and shared by the path planner tests."""
+"""The path planner's fixture cases (tests/golden/paths.{npz,json} and the edge group tests/golden/path_edges.{npz,json},
+both written by tools/gen_path_golden.py from the reference's own PathPlanner), loaded once and shared by the path
+planner tests."""
 import functools
 import json
 import os
 
 import numpy as np
 
+from abr_control_amd import _abi
 from abr_control_amd.controllers.path_planners import position_profiles, velocity_profiles
 
 _GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -17,21 +19,31 @@ MAIN = ("case1", "case2", "case3", "case4")
 
 
 @functools.lru_cache(maxsize=None)
-def golden():
-    meta = json.load(open(os.path.join(_GOLDEN, "paths.json")))
-    data = dict(np.load(os.path.join(_GOLDEN, "paths.npz")))
+def _pair(stem):
+    meta = json.load(open(os.path.join(_GOLDEN, f"{stem}.json")))
+    data = dict(np.load(os.path.join(_GOLDEN, f"{stem}.npz")))
     for v in data.values():
         v.setflags(write=False)
     return meta, data
 
 
+def golden(name=None):
+    """(meta, data) of the file pair that holds case `name`; of the first pair without a name"""
+    return _pair("path_edges" if name in _pair("path_edges")[0]["cases"] else "paths")
+
+
 def names():
-    return list(golden()[0]["cases"])
+    return list(_pair("paths")[0]["cases"]) + list(_pair("path_edges")[0]["cases"])
+
+
+def group(name):
+    """the cases of one group of the edge pair ('axes', 'slerp_edges', 'gimbal', ...)"""
+    return [n for n, c in _pair("path_edges")[0]["cases"].items() if c["group"] == name]
 
 
 def profiles(name, dt=None):
-    """fresh profile objects of a case (this package's classes)"""
-    meta, data = golden()
+    """fresh profile objects of a case (this package's classes), at the case's own dt unless one is given"""
+    meta, data = golden(name)
     case = meta["cases"][name]
     kind, kw = case["pos"]
     kw = json.loads(json.dumps(kw))
@@ -40,13 +52,13 @@ def profiles(name, dt=None):
     else:
         pos = getattr(position_profiles, kind)(**kw)
     kind, kw = case["vel"]
-    return pos, getattr(velocity_profiles, kind)(dt=meta["dt"] if dt is None else dt, **kw)
+    return pos, getattr(velocity_profiles, kind)(dt=case.get("dt", meta["dt"]) if dt is None else dt, **kw)
 
 
 def rows(name):
     """-> dict(start, target, so, to (None for a 6-wide case), nt, paths: list of the reference's [T, W] paths,
     kwargs: max_velocity / start_velocity / target_velocity, axes)"""
-    meta, data = golden()
+    meta, data = golden(name)
     case = meta["cases"][name]
     nt = data[f"{name}_n_timesteps"]
     cuts = np.cumsum(nt)[:-1]
@@ -61,9 +73,11 @@ def rows(name):
 
 def check_against_reference(name, path, nt, report):
     """path [B, Tmax, W], nt [B] of any implementation against the fixture: counts exact, values within BOUND on every
-    column, padding equal to the row's last point.  report(column group, max abs difference) gets the figures first."""
+    column, padding equal to the row's last point, no value that is not finite.  report(column group, max abs difference)
+    gets the figures first."""
     r = rows(name)
     assert np.array_equal(np.asarray(nt), r["nt"]), (name, nt, r["nt"])
+    assert np.isfinite(path).all(), name
     worst = np.zeros(path.shape[-1])
     for b, ref in enumerate(r["paths"]):
         T = len(ref)
@@ -73,3 +87,109 @@ def check_against_reference(name, path, nt, report):
         if lo < len(worst):
             report(f"{name} {label}", worst[lo:lo + 3].max())
     assert worst.max() < BOUND, (name, worst)
+
+
+# ---- a reference-free check of the orientation columns: what the Euler angles of a path MEAN, for every sequence
+def euler_rotation(angles, axes):
+    """the rotation matrix of three Euler angles in the sequence `axes` ('sxyz', 'rzxz', ...), composed from elementary
+    rotations: a static ('s') sequence turns about the fixed axes in the order given, so every later rotation
+    multiplies from the left; a rotating ('r') sequence turns about the axes it carries along, from the right"""
+    R = np.eye(3)
+    for angle, letter in zip(angles, axes[1:]):
+        u = "xyz".index(letter)
+        v, w = (u + 1) % 3, (u + 2) % 3
+        E = np.eye(3)
+        E[v, v] = E[w, w] = np.cos(angle)
+        E[w, v] = np.sin(angle)
+        E[v, w] = -np.sin(angle)
+        R = E @ R if axes[0] == "s" else R @ E
+    return R
+
+
+def euler_quaternion(angles, axes):
+    """the same composition as euler_rotation in quaternions (w, x, y, z), half angles multiplied up in the same order:
+    continuous in the angles and 1 at zero, so its sign is the one a SLERP of Euler angles starts from"""
+    q = np.array([1.0, 0.0, 0.0, 0.0])
+    mul = lambda a, b: np.concatenate([[a[0] * b[0] - a[1:] @ b[1:]],
+                                       a[0] * b[1:] + b[0] * a[1:] + np.cross(a[1:], b[1:])])
+    for angle, letter in zip(angles, axes[1:]):
+        e = np.zeros(4)
+        e[0], e[1 + "xyz".index(letter)] = np.cos(angle / 2), np.sin(angle / 2)
+        q = mul(e, q) if axes[0] == "s" else mul(q, e)
+    return q
+
+
+def rotation_angle(R):
+    """the angle of a rotation matrix in [0, pi], from its antisymmetric part and its trace (accurate at both ends,
+    where arccos of the trace alone resolves 1e-8)"""
+    s = 0.5 * np.sqrt((R[2, 1] - R[1, 2]) ** 2 + (R[0, 2] - R[2, 0]) ** 2 + (R[1, 0] - R[0, 1]) ** 2)
+    return np.arctan2(s, 0.5 * (np.trace(R) - 1.0))
+
+
+GEODESIC_BOUND = 1e-9
+GEODESIC_DT = 0.01
+
+
+@functools.lru_cache(maxsize=None)
+def geodesic_rows(axes):
+    """4 movements of 0.2-0.3 m with orientations in +-3 rad for a sequence (Linear + Gaussian(dt=0.01, acceleration=4))
+    -> start, target, start_orientation, target_orientation"""
+    r = np.random.RandomState(1000 + sorted(_abi.EULER_AXES).index(axes))
+    start = r.uniform(-0.4, 0.4, (4, 3))
+    d = r.normal(size=(4, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    out = start, start + d * r.uniform(0.2, 0.3, (4, 1)), r.uniform(-3, 3, (4, 3)), r.uniform(-3, 3, (4, 3))
+    while not euler_quaternion(out[2][3], axes) @ euler_quaternion(out[3][3], axes) < 0:  # one row at least needs the flip
+        out[2][3], out[3][3] = r.uniform(-3, 3, 3), r.uniform(-3, 3, 3)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def check_geodesic(axes, path, nt, so, to, report):
+    """path [B, Tmax, 12], nt [B] of any implementation: the rotation of the Euler columns equals that of the start
+    angles at step 0 and that of the target angles at step T - 1, and at every step lies on the shorter geodesic
+    between them at the fraction the position columns give (orientation.py:182-190) - all within GEODESIC_BOUND.
+    A SLERP that lost its d < 0 flip travels the longer arc and fails the fraction rule."""
+    worst = np.zeros(4)
+    for b in range(len(nt)):
+        T = int(nt[b])
+        rot = [euler_rotation(path[b, i, 6:9], axes) for i in range(T)]
+        R0, R1 = euler_rotation(so[b], axes), euler_rotation(to[b], axes)
+        total = rotation_angle(R0.T @ R1)
+        pos = path[b, :T, :3]
+        fraction = 1.0 - np.linalg.norm(pos[-1] - pos, axis=1) / np.linalg.norm(pos[-1] - pos[0])
+        ends = max(rotation_angle(R0.T @ rot[0]), rotation_angle(R1.T @ rot[-1]))
+        along = np.array([rotation_angle(R0.T @ R) for R in rot])
+        rest = np.array([rotation_angle(R.T @ R1) for R in rot])
+        worst = np.maximum(worst, [ends, np.abs(along + rest - total).max(), np.abs(along - fraction * total).max(), 0])
+        worst[3] = max(worst[3], total)
+    report(f"{axes} ends {worst[0]:.3e} on the geodesic {worst[1]:.3e} at the fraction {worst[2]:.3e} "
+           f"(largest angle {worst[3]:.4f})")
+    assert worst[3] <= np.pi and worst[:3].max() < GEODESIC_BOUND, (axes, worst)
+
+
+# ---- the two rows no fixture can hold
+def antidiagonal_batch():
+    """four 12-wide movements, the third exactly towards -(1,1,1)/sqrt(3): target = start - 0.25 (1,1,1)/sqrt(3) from
+    (0.1, -0.2, 0.3) -> start, target, start_orientation, target_orientation"""
+    r = np.random.RandomState(77)
+    start = r.uniform(-0.4, 0.4, (4, 3))
+    d = r.normal(size=(4, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    target = start + d * r.uniform(0.2, 0.3, (4, 1))
+    start[2] = (0.1, -0.2, 0.3)
+    target[2] = start[2] - 0.25 * (np.ones(3) / np.sqrt(3))
+    return start, target, r.uniform(-1, 1, (4, 3)), r.uniform(-1, 1, (4, 3))
+
+
+def check_truncated_fill(cut, full, nt, t_max, sentinel):
+    """cut [B, t_max, W]: the fill passes' output for a t_max below the largest step count, into an array that held
+    `sentinel`; full [B, max(nt), W]: the normal call.  A row that does not fit is untouched, the others are the
+    normal call's, cut at t_max, bit for bit."""
+    assert (nt > t_max).any() and (nt <= t_max).any()
+    for b in range(len(nt)):
+        if nt[b] > t_max:
+            assert np.array_equal(cut[b], np.full_like(cut[b], sentinel)), (b, nt[b], t_max)
+        else:
+            assert np.array_equal(cut[b], full[b, :t_max]), (b, nt[b], t_max)

@@ -1,8 +1,11 @@
 """The batched path planner on the GPU: every fixture case against the reference's own PathPlanner (step counts exact,
-all columns within tests/path_cases.BOUND, padding equal to the last point), rows independent of their batch bit for bit
-at 63 / 64 / 65 / 70 rows, the LDS and the global-scratch forms of the fill pass, the path feed recorded into a Plan, a
-closed loop { path_next; OSC; plant_step } replayed as a graph against the same calls fed from the host, and the error
-path of a row without a path.  Maxima observed on an MI355X: DESIGN.md "Path planner"."""
+all columns within tests/path_cases.BOUND, padding equal to the last point), the edge group of all 24 Euler sequences,
+SLERP branches and special directions included; the orientation columns of every sequence against rotations composed in
+NumPy; rows independent of their batch bit for bit at 63 / 64 / 65 / 70 rows, also where one batch mixes rows of one,
+two and three workgroup strides; the LDS and the global-scratch forms of the fill pass, the path feed recorded into a
+Plan, a closed loop { path_next; OSC; plant_step } replayed as a graph against the same calls fed from the host, the
+error path of a row without a path (start == target, a movement exactly towards -(1,1,1)/sqrt(3)) and a t_max below a
+row's step count.  Maxima observed on an MI355X: DESIGN.md "Path planner"."""
 import functools
 
 import numpy as np
@@ -21,14 +24,20 @@ def _planner(name, **kw):
 
 
 def _draw(name, B, seed):
-    """B rows with the settings of a fixture case: start in +-0.4, direction uniform on the sphere, the case's lengths"""
-    meta, _ = path_cases.golden()
-    lo, hi = meta["cases"][name]["length"]
+    """B rows with the settings of a fixture case: start in +-0.4, direction uniform on the sphere, the case's lengths.
+    'ragged' (dt = 0.001): the three fixture rows - under 64, 257-511 and over 512 steps - then B - 3 rows of 0.0025-0.25 m"""
+    meta, _ = path_cases.golden(name)
+    fixed = path_cases.rows(name) if name == "ragged" else None
+    lo, hi = (0.0025, 0.25) if fixed else meta["cases"][name]["length"]
     r = np.random.RandomState(seed)
-    start = r.uniform(-0.4, 0.4, (B, 3))
-    d = r.normal(size=(B, 3))
+    n = B - 3 if fixed else B
+    start = r.uniform(-0.4, 0.4, (n, 3))
+    d = r.normal(size=(n, 3))
     d /= np.linalg.norm(d, axis=1, keepdims=True)
-    return start, start + d * r.uniform(lo, hi, (B, 1)), r.uniform(-1, 1, (B, 3)), r.uniform(-1, 1, (B, 3))
+    out = start, start + d * r.uniform(lo, hi, (n, 1)), r.uniform(-1, 1, (n, 3)), r.uniform(-1, 1, (n, 3))
+    if fixed:
+        out = tuple(np.concatenate([f, o]) for f, o in zip((fixed["start"], fixed["target"], fixed["so"], fixed["to"]), out))
+    return out
 
 
 @pytest.mark.parametrize("name", path_cases.names())
@@ -60,16 +69,20 @@ def test_gpu_fixture_cases(name):
         assert np.array_equal(planner.orientation_path, one[:, 6:9]) and planner.ang_velocity_path.shape == (len(one), 3)
 
 
-@pytest.mark.parametrize("name", path_cases.MAIN)
+@pytest.mark.parametrize("name", path_cases.MAIN + ("ragged",))
 def test_gpu_rows_do_not_depend_on_their_batch_bitwise(name):
     """(b) 70 ragged rows with a case's settings: every row equals its own single-row run bit for bit, and so do the
-    rows of the 63-, 64- and 65-row batches (either side of a wavefront of the plan pass)"""
+    rows of the 63-, 64- and 65-row batches (either side of a wavefront of the plan pass).  'ragged': rows shorter than
+    a wavefront beside rows of two and of three workgroup strides, so the padding is wider than a stride"""
     start, target, so, to = _draw(name, 70, 70)
     kw = path_cases.rows(name)["kwargs"]
     planner = _planner(name)
     full = planner.generate_path(start, target, start_orientation=so, target_orientation=to, **kw).copy()
     nt = planner.n_timesteps.copy()
     assert nt.min() >= 2 and len(set(nt.tolist())) > 20  # ragged
+    if name == "ragged":
+        assert np.array_equal(nt[:3], path_cases.rows(name)["nt"]) and nt[0] < 64 and 256 < nt[1] < 512 < nt[2]
+        assert nt.max() - nt.min() > 256
     for b in range(70):
         one = planner.generate_path(start[b], target[b], start_orientation=so[b], target_orientation=to[b], **kw)
         assert planner.n_timesteps == nt[b] and np.array_equal(one, full[b, :nt[b]]), b
@@ -194,6 +207,84 @@ def test_gpu_closed_loop_follows_the_path_as_a_graph():
         assert np.array_equal(x.numpy(s), y.numpy(s))
     assert np.array_equal(counter.numpy(s), np.full(B, K)) and np.isfinite(q_g.numpy(s)).all()
     assert np.abs(q_g.numpy(s) - q0).max() > 1e-4  # the arms moved
+
+
+@pytest.mark.parametrize("axes", sorted(_abi.EULER_AXES))
+def test_gpu_orientation_columns_lie_on_the_geodesic(axes):
+    """(g) no reference involved: the Euler columns of every sequence, turned into rotations by NumPy, start and end at
+    the given orientations and walk the shorter geodesic between them at the fraction the position columns give"""
+    start, target, so, to = path_cases.geodesic_rows(axes)
+    planner = PathPlanner(position_profiles.Linear(), velocity_profiles.Gaussian(dt=path_cases.GEODESIC_DT, acceleration=4),
+                          axes=axes)
+    path = planner.generate_path(start, target, 1.0, start_orientation=so, target_orientation=to)
+    path_cases.check_geodesic(axes, path, planner.n_timesteps, so, to, lambda line: print("gpu", line))
+
+
+def test_gpu_no_path_exactly_towards_the_antidiagonal():
+    """(h) a movement exactly towards -(1,1,1)/sqrt(3) (align_vectors divides by 1 + cs = 0; the reference raises) in a
+    batch of four: ValueError, the same stream plans the next batch normally, and at the C ABI on host arrays
+    n_timesteps marks that row alone"""
+    import ctypes as C
+
+    import abr_control_amd as a
+    from abr_control_amd import engine
+    from abr_control_amd._lib import PathError, lib
+    from abr_control_amd.controllers.path_planners.path_planner import profile_tables
+
+    start, target, so, to = path_cases.antidiagonal_batch()
+    s = a.Stream(0)
+    pos, vel = position_profiles.Linear(), velocity_profiles.Gaussian(dt=0.004, acceleration=4)
+    planner = PathPlanner(pos, vel, stream=s)
+    with pytest.raises(ValueError) as ei:
+        planner.generate_path(start, target, 1.0, start_orientation=so, target_orientation=to)
+    assert isinstance(ei.value, PathError) and ei.value.code == _abi.EPATH
+    s.sync()  # reported once, by the call itself
+    keep = [0, 1, 3]
+    path = planner.generate_path(start[keep], target[keep], 1.0, start_orientation=so[keep], target_orientation=to[keep])
+    nt = planner.n_timesteps.copy()
+    assert nt.min() >= 2 and np.isfinite(path).all()
+    assert np.abs(path[np.arange(3), nt - 1, :3] - target[keep]).max() < 0.01  # (the bound of the reference's own warning)
+    table, off, cands = profile_tables(pos, vel, 1.0)
+    P = _abi.PathParams(vel.dt, pos.n_sample_points, len(cands), 22, 12, table.size)
+    with pytest.raises(PathError):
+        engine.path_plan(P, table, off, start, target)
+    nt4, rowplan, ds = np.full(4, -1, np.int32), np.zeros((4, 2), np.int32), np.zeros((4, pos.n_sample_points))
+    rc = lib().abrk_path_plan_batch(C.byref(P), table.ctypes.data, off.ctypes.data, 4, start.ctypes.data,
+                                    target.ctypes.data, nt4.ctypes.data, rowplan.ctypes.data, ds.ctypes.data, 0, None)
+    assert rc == _abi.EPATH and nt4[2] == 0 and np.array_equal(nt4[keep], nt)
+    # the fill passes leave that row alone and give the others what the batch of three got
+    out = engine.path_fill(P, table, off, int(nt.max()), start, target, nt4, rowplan, ds, so, to)
+    assert np.array_equal(out[keep], path)
+
+
+def test_gpu_t_max_below_a_rows_step_count():
+    """(i) engine.path_fill with t_max = max(n_timesteps) - 1 on the rows of case1, into a DeviceArray that holds a
+    sentinel: a row that does not fit keeps the sentinel in every column (it used to get a truncated path without
+    velocity columns), the others equal the normal call's rows cut at t_max bit for bit - and the host build of the row
+    programs, which the device is to follow here, gives the same array"""
+    import abr_control_amd as a
+    from abr_control_amd import engine
+    from abr_control_amd.controllers.path_planners.path_planner import profile_tables
+    from tests import hostsim_path
+
+    r = path_cases.rows("case1")
+    pos, vel = path_cases.profiles("case1")
+    table, off, cands = profile_tables(pos, vel, r["kwargs"]["max_velocity"])
+    P = _abi.PathParams(vel.dt, pos.n_sample_points, len(cands), _abi.euler_axes_code(r["axes"]), 12, table.size)
+    s = a.Stream(0)
+    up = lambda h: a.DeviceArray.from_numpy(np.ascontiguousarray(h))
+    d_table, d_start, d_target, d_so, d_to = up(table), up(r["start"]), up(r["target"]), up(r["so"]), up(r["to"])
+    nt_d, rowplan_d, ds_d = engine.path_plan(P, d_table, off, d_start, d_target, stream=s)
+    nt = nt_d.numpy(s)
+    assert np.array_equal(nt, r["nt"])
+    t_max = int(nt.max()) - 1
+    B = len(nt)
+    full = engine.path_fill(P, d_table, off, t_max + 1, d_start, d_target, nt_d, rowplan_d, ds_d, d_so, d_to, stream=s)
+    cut = engine.path_fill(P, d_table, off, t_max, d_start, d_target, nt_d, rowplan_d, ds_d, d_so, d_to,
+                           path=up(np.full((B, t_max, 12), -7.0)), stream=s)
+    path_cases.check_truncated_fill(cut.numpy(s), full.numpy(s), nt, t_max, -7.0)
+    model = hostsim_path.fill(pos, vel, r["start"], r["target"], r["so"], r["to"], t_max, sentinel=-7.0, **r["kwargs"])
+    assert np.array_equal(model == -7.0, cut.numpy(s) == -7.0) and np.abs(model - cut.numpy(s)).max() < path_cases.BOUND
 
 
 def test_gpu_row_without_a_path_raises_value_error():

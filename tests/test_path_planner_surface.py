@@ -74,7 +74,7 @@ def test_surface_mirrors_reference():
 
 @pytest.mark.parametrize("name", path_cases.names())
 def test_profiles_equal_the_reference_tables_bit_for_bit(name):
-    meta, data = path_cases.golden()
+    meta, data = path_cases.golden(name)
     case = meta["cases"][name]
     pos, vel = path_cases.profiles(name)
     samples = np.array([pos.step(t) for t in np.linspace(0, 1, pos.n_sample_points)], dtype=float)
