@@ -248,6 +248,58 @@ def make_plant_params(dt, substeps=1, gravity=True):
     return p
 
 
+FX_SATURATION, FX_VISCOUS, FX_COULOMB, FX_LIMITS = 1, 2, 4, 8  # ABRK_FX_* (include/abrk.h)
+
+
+class PlantEffects(C.Structure):
+    """abrk_plant_effects (include/abrk.h)"""
+    _fields_ = [("flags", C.c_uint32), ("damping", C.c_double * MAX_JOINTS), ("coulomb", C.c_double * MAX_JOINTS),
+                ("coulomb_vs", C.c_double), ("tau_max", C.c_double * MAX_JOINTS), ("q_min", C.c_double * MAX_JOINTS),
+                ("q_max", C.c_double * MAX_JOINTS), ("restitution", C.c_double)]
+
+
+def make_plant_effects(n, damping=None, coulomb=None, coulomb_vs=None, tau_max=None, q_min=None, q_max=None,
+                       restitution=0.0):
+    """The non-ideal effects of engine.plant_step / forward_dynamics for an arm of `n` joints.  Each per-joint argument
+    is a scalar (every joint) or a sequence of n values; None leaves the effect's flag off.  damping: viscous friction
+    -b dq; coulomb with coulomb_vs: -c dq / sqrt(dq^2 + vs^2); tau_max: |u| clamped; q_min and q_max (both): hard joint
+    limits with the coefficient of restitution `restitution`.  The values are checked by the C entry point."""
+    n = int(n)
+    if not 1 <= n <= MAX_JOINTS:
+        raise ValueError(f"n={n} outside 1..{MAX_JOINTS}")
+    p = PlantEffects()
+
+    def fill(field, value, name):
+        v = np.asarray(value, dtype=float)
+        if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != n):
+            raise ValueError(f"{name} must be a scalar or {n} values, got shape {v.shape}")
+        for i, x in enumerate(np.broadcast_to(v, (n,))):
+            field[i] = x
+
+    if damping is not None:
+        fill(p.damping, damping, "damping")
+        p.flags |= FX_VISCOUS
+    if coulomb is not None:
+        if coulomb_vs is None:
+            raise ValueError("coulomb friction needs coulomb_vs, the speed below which it fades to zero")
+        fill(p.coulomb, coulomb, "coulomb")
+        p.coulomb_vs = float(coulomb_vs)
+        p.flags |= FX_COULOMB
+    elif coulomb_vs is not None:
+        p.coulomb_vs = float(coulomb_vs)
+    if tau_max is not None:
+        fill(p.tau_max, tau_max, "tau_max")
+        p.flags |= FX_SATURATION
+    if (q_min is None) != (q_max is None):
+        raise ValueError("joint limits need both q_min and q_max")
+    if q_min is not None:
+        fill(p.q_min, q_min, "q_min")
+        fill(p.q_max, q_max, "q_max")
+        p.flags |= FX_LIMITS
+    p.restitution = float(restitution)
+    return p
+
+
 class TraceParams(C.Structure):
     """abrk_trace_params (include/abrk.h)"""
     _fields_ = [("frame", C.c_int32), ("x_off", C.c_double * 3), ("every", C.c_int32), ("capacity", C.c_int32),

@@ -2,14 +2,16 @@
 connect / disconnect / reset / get_feedback / send_forces, for one arm (q of shape (n,)) or B arms (q_init of shape
 (B, n)), stepped on the GPU by engine.plant_step: ddq = M^-1 (u - C dq - g) with the robot_config's own M, C and g, then
 dq += ddq h, q += dq h, `substeps` times per call with h = dt / substeps (arms/threejoint/arm_sim.py:93-94 takes
-dt / 1e-5 such substeps).  No joint friction, joint limits or contacts."""
+dt / 1e-5 such substeps).  `effects` (_abi.make_plant_effects) makes the plant non-ideal: torque saturation, viscous and
+smoothed Coulomb joint friction, hard joint limits with restitution; send_forces also takes a joint-space disturbance
+`tau_ext` and a world-frame wrench at the end effector (include/abrk.h, abrk_plant_effects).  No contacts."""
 import numpy as np
 
 from .. import _abi, engine
 
 
 class ArmSim:
-    def __init__(self, robot_config, dt=0.001, q_init=None, substeps=1, gravity=True):
+    def __init__(self, robot_config, dt=0.001, q_init=None, substeps=1, gravity=True, effects=None):
         self.robot_config = robot_config
         n = robot_config.N_JOINTS
         q0 = q_init if q_init is not None else getattr(robot_config, "START_ANGLES", None)
@@ -19,6 +21,7 @@ class ArmSim:
         self.dt = dt
         self.substeps = int(substeps)
         self.gravity = bool(gravity)
+        self.effects = effects
         self.t = 0.0
         self.reset()
 
@@ -35,8 +38,9 @@ class ArmSim:
     def get_feedback(self):
         return {"q": self.q, "dq": self.dq}
 
-    def send_forces(self, u, dt=None):
-        """advance one time step under torques u (arm_sim.py:67-82)"""
+    def send_forces(self, u, dt=None, tau_ext=None, wrench=None):
+        """advance one time step under torques u (arm_sim.py:67-82); tau_ext (n,) or (B, n) and wrench (6,) or (B, 6) are
+        loads the controller does not know of"""
         rc = self.robot_config
         dtype = np.dtype(getattr(rc, "dtype", np.float64))
         single = self.q.ndim == 1
@@ -44,6 +48,13 @@ class ArmSim:
         dq = np.array(np.atleast_2d(self.dq), dtype=dtype, order="C")
         u2 = np.ascontiguousarray(np.broadcast_to(np.atleast_2d(np.asarray(u, dtype=dtype)), q.shape))
         params = _abi.make_plant_params(self.dt if dt is None else dt, self.substeps, self.gravity)
-        engine.plant_step(rc.arm_id, rc.N_JOINTS, params, q, dq, u2, dtype=dtype, device=rc.device)
+
+        def rows(x, w):
+            if x is None:
+                return None
+            return np.ascontiguousarray(np.broadcast_to(np.atleast_2d(np.asarray(x, dtype=dtype)), (q.shape[0], w)))
+
+        engine.plant_step(rc.arm_id, rc.N_JOINTS, params, q, dq, u2, dtype=dtype, device=rc.device, effects=self.effects,
+                          tau_ext=rows(tau_ext, q.shape[1]), wrench=rows(wrench, 6))
         self.q, self.dq = (q[0], dq[0]) if single else (q, dq)
         self.t += self.dt

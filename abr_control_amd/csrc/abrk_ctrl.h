@@ -2147,6 +2147,213 @@ ABRK_INL void plant_row(const A& arm, T h, int substeps, bool gravity, bool inte
   }
 }
 
+// ---------------------------------------------------------------- the same plant with non-ideal effects, one row
+// Per substep, with q and dq as they are at its start (include/abrk.h, abrk_plant_effects):
+//   tau = clamp(u, -tau_max, +tau_max) + tau_ext + J("EE", q)^T w - b dq - c dq / sqrt(dq^2 + v_s^2)
+//   ddq = M^-1 (tau - C dq - g);  dq += ddq h;  q += dq h
+//   q_i beyond a limit: q_i = the limit, and a dq_i that points outwards becomes -e dq_i
+// Every effect is runtime and uniform over the launch (one instantiation per arm and type), and the row takes NO branch
+// on them: a branch inside the substep loop costs the six-joint fp64 kernel its two-wave budget (70 registers spilled
+// for one `if` around the limit step alone, profiles/plant_step.md).  An effect that is off arrives as the constant that
+// leaves the row's values as they are - tau_max and the limits at the largest finite number, damping and coulomb 0,
+// on_ext / on_w 0 - so with all of them off the row has the bits of plant_row.
+// Three phases per substep.  A: tau from u, the loads and the friction; the wrench torque needs Joints::z / ::o, which a
+// forward-kinematics pass of its own provides (~6 % of the row's operations) - taken from the dynamics pass instead, the
+// wrench code sits where that pass holds M, g and the Coriolis vector, and spills.  tau is parked (LDS in the kernels).
+// B: the dynamics pass and the solve of plant_row, statement for statement, reading the parked tau where plant_row
+// reads u.  C: the update and the limits.
+// The constants reach the row as a flat table it reads where a phase consumes them (LDS in the kernels): held in scalar
+// registers across the loop, the 34 values of a six-joint arm take 68 of the ~100 that the dynamics pass already fills
+// with its own constants, and the overflow lands in vector registers.
+template <class T>
+struct PlantFxP {
+  enum : int {
+    kJ = 7,  // ABRK_MAX_JOINTS
+    DAMP = 0, COUL = kJ, TMAX = 2 * kJ, QMIN = 3 * kJ, QMAX = 4 * kJ,  // per joint
+    VS2 = 5 * kJ,   // coulomb_vs^2 (1 where Coulomb friction is off)
+    REST,           // restitution
+    ON_EXT, ON_W,   // 1 where the call has a tau_ext / a wrench array, else 0
+    COUNT
+  };
+  T c[COUNT];
+};
+// `p` again, for the optimiser a pointer whose reads it cannot move out of the loop or merge with earlier ones - but, unlike
+// opaque(p), still one into p's address space (an LDS read, not a flat one) and no 64-bit value held across the loop
+template <class P>
+ABRK_INL P* reread(P* p) {
+  int z = 0;
+  opaque(z);
+  return p + z;
+}
+// where a row's tau waits between phases A and B: element i at p[i * stride]
+template <class T>
+struct FxPark {
+  T* p;
+  int stride;
+};
+template <class T, int N>
+struct ScUseRev {
+  const T (&sv)[N][2];
+  template <int I>
+  ABRK_INL void get(T, T& s, T& c) const {
+    s = sv[N - 1 - I][1];
+    c = sv[N - 1 - I][0];
+  }
+};
+template <class A, class T, class GetU, class GetExt, class GetW, class Scr>
+ABRK_INL void plant_fx_row(const A& arm, T h, int substeps, bool gravity, bool integrate, const T* fxc,
+                           T (&q)[A::N], T (&dq)[A::N], GetU&& get_u, GetExt&& get_ext, GetW&& get_w,
+                           const FxPark<T>& park, T (&ddq)[A::N], T& minpiv, Scr& scr) {
+  constexpr int N = A::N;
+  using F = PlantFxP<T>;
+  static_assert(N <= F::kJ, "PlantFxP holds kJ constants per effect");
+  constexpr bool REC = kRecursiveC<A, CMODE_VEC>;
+  // The friction torque of a substep depends on dq at its start - the dq that phase C of the substep before leaves - so
+  // it is formed there (and once ahead of the loop) and waits in the parking place: phase A then reads no dq at all.  A
+  // read of dq in front of the dynamics pass changes where the optimiser extracts its elements, with that the order of
+  // the operands of the pass's commutative operations, and with that the last bit of some fused multiply-adds.
+  auto park_friction = [&](const T(&dqv)[N]) ABRK_LAMBDA {
+    const T* c = reread(fxc);
+    sfor<N>([&](auto i) ABRK_LAMBDA {
+      const T ir = Rm<T>::rsqrt(Rm<T>::fma(dqv[i()], dqv[i()], c[F::VS2]));
+      park.p[i() * park.stride] = Rm<T>::fma(-c[F::COUL + i()] * dqv[i()], ir, -c[F::DAMP + i()] * dqv[i()]);
+    });
+  };
+  park_friction(dq);
+  for (int s = 0; s < substeps; s++) {
+    // the main path of sincos_all_tab / sincos_all (the same bits as the OSC kernels' pass)
+    T sv[N][2];
+    bool all_in = true;
+    sfor<N>([&](auto i) ABRK_LAMBDA {
+      if constexpr (std::remove_reference<Scr>::type::kHasTab) {
+        all_in = all_in && Rm<T>::sincos_tab_in_range(q[i()]);
+        Rm<T>::sincos_tab(q[i()], scr.sctab, sv[i()][0], sv[i()][1]);
+      } else {
+        all_in = all_in && Rm<T>::sincos_in_range(q[i()]);
+        Rm<T>::sincos_fast(q[i()], sv[i()][0], sv[i()][1]);
+      }
+    });
+    NoCap nc;
+    // ---- A: tau
+    {
+      T tau[N], ext[N];
+      const T* c = reread(fxc);
+      get_u(tau);
+      sfor<N>([&](auto i) ABRK_LAMBDA {
+        tau[i()] = Rm<T>::fmin(Rm<T>::fmax(tau[i()], -c[F::TMAX + i()]), c[F::TMAX + i()]);
+      });
+      get_ext(ext);
+      sfor<N>([&](auto i) ABRK_LAMBDA { tau[i()] = Rm<T>::fma(c[F::ON_EXT], ext[i()], tau[i()]); });
+      {
+        // (J^T w)_i = (W_i (p_EE - o_i)) . f + z_i . m: column i of robot_config.J("EE", q) against the wrench
+        // (from copies of sin / cos the optimiser knows nothing of: it would otherwise merge this chain with the one
+        // of phase B and carry its results - Joints, 36 values - into the dynamics pass)
+        Joints<A, T> jk;
+        T KR[9], ko[3], pe[3], w[6], sk[N][2];
+        bool in_a = true;
+        sfor<N>([&](auto i) ABRK_LAMBDA {
+          T qa = q[i()];
+          opaque(qa);
+          if constexpr (std::remove_reference<Scr>::type::kHasTab) {
+            in_a = in_a && Rm<T>::sincos_tab_in_range(qa);
+            Rm<T>::sincos_tab(qa, scr.sctab, sk[i()][0], sk[i()][1]);
+          } else {
+            in_a = in_a && Rm<T>::sincos_in_range(qa);
+            Rm<T>::sincos_fast(qa, sk[i()][0], sk[i()][1]);
+          }
+        });
+        if (!in_a)
+          sfor<N>([&](auto i) ABRK_LAMBDA {
+            const SinCosPair<T> r = sincos_out_of_line(q[i()]);
+            sk[i()][0] = r.s;
+            sk[i()][1] = r.c;
+          });
+        fk_forward(arm, q, jk, KR, ko, nc, [](auto, const T(&)[3]) ABRK_LAMBDA {}, ScUse<T, N>{sk});
+        mulBE_pt<A, T>(arm, KR, ko, pe);
+        get_w(w);
+        const T f[3] = {w[0], w[1], w[2]}, m[3] = {w[3], w[4], w[5]};
+        sfor<N>([&](auto i) ABRK_LAMBDA {
+          const T dl[3] = {pe[0] - jk.o[i()][0], pe[1] - jk.o[i()][1], pe[2] - jk.o[i()][2]};
+          T e[3];
+          wapply<i()>(jk, dl, e);
+          tau[i()] = Rm<T>::fma(c[F::ON_W], dot3(e, f) + dot3(jk.z[i()], m), tau[i()]);
+        });
+      }
+      {
+        const T* fr = reread(park.p);  // the friction torque, parked by phase C of the substep before
+        sfor<N>([&](auto i) ABRK_LAMBDA { tau[i()] += fr[i() * park.stride]; });
+      }
+      sfor<N>([&](auto i) ABRK_LAMBDA { park.p[i() * park.stride] = tau[i()]; });
+    }
+    ABRK_SCHED_FENCE();
+    // The dynamics pass must come out of the compiler as it does in plant_row, to the last bit.  The optimiser orders the
+    // operands of commutative operations by where their inputs are defined, and instruction selection fuses
+    // a * b + c * d into fma(a, b, c * d) or fma(c, d, a * b) by that order (with phase A in front and sin / cos settled
+    // before it, general chains came out one unit in the last place off plant_row on about one value in 500).  So the
+    // out-of-range angles are redone HERE, in plant_row's own statements: phase B starts a basic block of its own with the
+    // merges of the two sin / cos paths at its head, as plant_row's does.  Phase A redid them for its own copies.
+    T svr[N][2];
+    sfor<N>([&](auto i) ABRK_LAMBDA {
+      svr[N - 1 - i()][1] = sv[i()][0];
+      svr[N - 1 - i()][0] = sv[i()][1];
+    });
+    if (!all_in)
+      sfor<N>([&](auto i) ABRK_LAMBDA {
+        const SinCosPair<T> r = sincos_out_of_line(q[i()]);
+        svr[N - 1 - i()][1] = r.s;
+        svr[N - 1 - i()][0] = r.c;
+      });
+    const ScUseRev<T, N> sincos_policy{svr};
+    // ---- B: the dynamics pass of plant_row
+    Joints<A, T> jt;
+    Dyn<A, T, REC ? CMODE_NONE : CMODE_VEC> d;
+    T XR[9], xo[3], cv2[REC ? N : 1];
+    if constexpr (REC) {
+      RneState<T> rne;
+      rne_init(rne);
+      kin_dyn_hook(arm, q, dq, jt, d, XR, xo, nc, [&](auto L, const T(&pl)[3]) ABRK_LAMBDA {
+        ABRK_SCHED_FENCE();
+        rne_forward_step<L()>(arm, jt, pl, dq, rne, scr);
+        ABRK_SCHED_FENCE();
+      }, sincos_policy);
+      rne_backward(jt, scr, cv2);
+    } else {
+      kin_dyn_hook(arm, q, dq, jt, d, XR, xo, nc, [](auto, const T(&)[3]) ABRK_LAMBDA {}, sincos_policy);
+    }
+    ABRK_SCHED_FENCE();
+    T rhs[N], y[N], tau[N];
+    {
+      const T* pp = reread(park.p);  // (not forwarded from the stores of phase A: tau stays parked until here)
+      sfor<N>([&](auto i) ABRK_LAMBDA { tau[i()] = pp[i() * park.stride]; });
+    }
+    sfor<N>([&](auto i) ABRK_LAMBDA {
+      if constexpr (REC) rhs[i()] = Rm<T>::fma(T(-1), cv2[i()], tau[i()]);
+      else rhs[i()] = Rm<T>::fma(T(-1), d.cv[i()], tau[i()]);
+    });
+    if (gravity) sfor<N>([&](auto i) ABRK_LAMBDA { rhs[i()] = Rm<T>::fma(T(9.81), d.gz[i()], rhs[i()]); });
+    T L[N * (N + 1) / 2], il[N];
+    chol<N, T, false>(d.Ms, L, il, &minpiv);
+    chol_fwd<N>(L, il, rhs, y);
+    chol_bwd<N>(L, il, y, ddq);
+    if (!integrate) break;
+    // ---- C: the update, then the limits
+    const T* c = reread(fxc);
+    const T bounce = -c[F::REST];  // read ahead of the selects: a load in a select's arm makes it a branch
+    sfor<N>([&](auto i) ABRK_LAMBDA {
+      dq[i()] = Rm<T>::fma(ddq[i()], h, dq[i()]);
+      q[i()] = Rm<T>::fma(dq[i()], h, q[i()]);
+      // (min / max and one factor per joint: written as conditional assignments the compiler makes them six
+      // divergent branches)
+      const T lo = c[F::QMIN + i()], hi = c[F::QMAX + i()];
+      // (& and | on purpose: a short-circuit && / || here becomes two divergent branches per joint)
+      const bool out = ((int(q[i()] > hi) & int(dq[i()] > T(0))) | (int(q[i()] < lo) & int(dq[i()] < T(0)))) != 0;
+      q[i()] = Rm<T>::fmin(Rm<T>::fmax(q[i()], lo), hi);
+      dq[i()] = out ? bounce * dq[i()] : dq[i()];  // e = 0: a zero
+    });
+    park_friction(dq);
+  }
+}
+
 // ---------------------------------------------------------------- InverseKinematics.generate_path, one row
 // (controllers/path_planners/inverse_kinematics.py:84-135): n_steps sequential iterations, q in registers.
 template <class A, class T>

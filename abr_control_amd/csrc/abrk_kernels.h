@@ -489,6 +489,33 @@ plant_kernel(A arm, PlantP<T> P, long B, T* __restrict__ qg, T* __restrict__ dqg
   plant_body<A, T>(b, arm, P, qg, dqg, ug, ddqg, scr);
 }
 
+// The plant with joint friction, limits, torque saturation and external loads (abrk_ctrl.h plant_fx_row): a kernel of
+// its own beside plant_kernel, one instantiation per (arm, type) - the effects are runtime constants in F, uniform over
+// the launch.  The LDS layout and the budget of plant_kernel, plus N values per lane where tau waits for the dynamics
+// pass (3 KiB for a six-joint fp64 arm).
+template <class A, class T>
+__global__ void __launch_bounds__(kBlock, osc_min_waves(3, true, 0, osc_ortho<A>(), 0, A::kStatic))
+plant_fx_kernel(A arm, PlantP<T> P, PlantFxP<T> F, long B, T* __restrict__ qg, T* __restrict__ dqg,
+                const T* __restrict__ ug, const T* __restrict__ extg, const T* __restrict__ wg, T* __restrict__ ddqg) {
+  constexpr bool kLds = plant_uses_slab<A>();
+  using V2 = typename LdsScratch<T, A::N>::V2;
+  __shared__ T sctab[2 * kSinCosN];
+  __shared__ T fxc[PlantFxP<T>::COUNT];  // every lane writes the same values: no index into the kernel arguments
+  for (int k = 0; k < PlantFxP<T>::COUNT; k++) fxc[k] = F.c[k];
+  load_sincos_table(sctab, (int)threadIdx.x);  // every lane takes part: before any exit (it ends with the barrier)
+  __shared__ V2 slab[kLds ? 3 * A::N * kBlock : 1];
+  ABRK_ROW_INDEX
+  std::conditional_t<kLds, LdsScratch<T, A::N>, TabScratch<T, A::N>> scr;
+  if constexpr (kLds) {
+    scr.slab = slab;
+    scr.lane = (int)threadIdx.x;
+  }
+  scr.sctab = sctab;
+  __shared__ T taus[A::N * kBlock];  // [N][kBlock]: a lane's values kBlock apart, no bank conflict
+  const FxPark<T> park{taus + threadIdx.x, kBlock};
+  plant_fx_body<A, T>(b, arm, P, fxc, qg, dqg, ug, extg, wg, ddqg, park, scr);
+}
+
 // The loop recorder (abrk_trace.h trace_body): forward kinematics only, so two waves per SIMD without scratch.
 // History rows of a wavefront whose rows share one slot - every wavefront, until a caller restarts some rows on their
 // own - are parked in LDS laid out like the slot's 64-row block of the history and streamed out linearly: 16 bytes per
@@ -717,6 +744,12 @@ struct PlantArgs {
   const void* u;
   void* ddq;      // mode 0: the output
 };
+struct PlantFxArgs {
+  const void *P, *F;  // PlantP<T>, PlantFxP<T>
+  void *q, *dq;
+  const void *u, *tau_ext, *wrench;  // tau_ext [B, N] and wrench [B, 6] may be null
+  void* ddq;
+};
 struct TraceArgs {
   const void* P;  // TraceP<T>
   const void *q, *dq, *u, *target;
@@ -773,6 +806,7 @@ struct ArmOps {
   hipError_t (*obstacles)(int dtype, const LaunchArgs&, const ObstaclesArgs&);
   hipError_t (*plant)(int dtype, const LaunchArgs&, const PlantArgs&);
   hipError_t (*trace)(int dtype, const LaunchArgs&, const TraceArgs&);
+  hipError_t (*plant_fx)(int dtype, const LaunchArgs&, const PlantFxArgs&);
 };
 hipError_t launch_twolink_step(int dtype, const LaunchArgs& la, const void* K, void* q, void* dq, const void* u);
 
@@ -933,6 +967,12 @@ struct Launch {
                        *static_cast<const PlantP<T>*>(a.P), la.B, (T*)a.q, (T*)a.dq, (const T*)a.u, (T*)a.ddq);
     return hipGetLastError();
   }
+  static hipError_t plant_fx(const LaunchArgs& la, const PlantFxArgs& a) {
+    hipLaunchKernelGGL((plant_fx_kernel<A, T>), grid_for(la.B), dim3(kBlock), 0, la.stream, arm_of(la),
+                       *static_cast<const PlantP<T>*>(a.P), *static_cast<const PlantFxP<T>*>(a.F), la.B, (T*)a.q,
+                       (T*)a.dq, (const T*)a.u, (const T*)a.tau_ext, (const T*)a.wrench, (T*)a.ddq);
+    return hipGetLastError();
+  }
   static hipError_t trace(const LaunchArgs& la, const TraceArgs& a) {
     // measurement switch: the row-per-lane history stores for every wavefront (profiles/loop_trace.md)
     static const bool plain = measurement_env("ABRK_TRACE_PLAIN") != nullptr;
@@ -1029,9 +1069,12 @@ struct OpsFor {
   static hipError_t trace(int dt, const LaunchArgs& la, const TraceArgs& a) {
     return dt == 0 ? Launch<AD, double>::trace(la, a) : Launch<AF, float>::trace(la, a);
   }
+  static hipError_t plant_fx(int dt, const LaunchArgs& la, const PlantFxArgs& a) {
+    return dt == 0 ? Launch<AD, double>::plant_fx(la, a) : Launch<AF, float>::plant_fx(la, a);
+  }
   static const ArmOps* ops() {
     static const ArmOps o = {AD::N, &dyn, &osc, &sliding, &joint, AD::N == 2 ? &rollout : nullptr, &ik,
-                             &floating, &obstacles, &plant, &trace};
+                             &floating, &obstacles, &plant, &trace, &plant_fx};
     return &o;
   }
 };

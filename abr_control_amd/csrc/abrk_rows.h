@@ -541,6 +541,46 @@ ABRK_INL void plant_body(long b, const A& arm, const PlantP<T>& P, T* __restrict
   if (any_lane(!(minpiv > T(0))) && P.status) *P.status = 1;
 }
 
+// ---- the plant with non-ideal effects (abrk_ctrl.h plant_fx_row): plant_body plus per-row loads.  `extg` [B, N] and
+// `wg` [B, 6] may each be null (uniform); like u they are read where a substep consumes them, so a recorded plan sees
+// what its caller last wrote into them.  No branch on a null array (plant_fx_row): its reads go to the row's u instead -
+// always there, N >= 1 values - and ON_EXT / ON_W = 0 in the constants `fxc` (PlantFxP::c) takes them out of the sum.
+template <class A, class T, class Scr>
+ABRK_INL void plant_fx_body(long b, const A& arm, const PlantP<T>& P, const T* fxc, T* __restrict__ qg,
+                            T* __restrict__ dqg, const T* __restrict__ ug, const T* __restrict__ extg,
+                            const T* __restrict__ wg, T* __restrict__ ddqg, const FxPark<T>& park, Scr& scr) {
+  constexpr int N = A::N;
+  T q[N], dq[N], ddq[N];
+  load_row<N>(qg, b, q);
+  load_row<N>(dqg, b, dq);
+  // Row addresses are formed where they are used, from a copy of b the optimiser cannot see through (row()): formed
+  // ahead of the loop, each is one more 64-bit value held across the dynamics pass - and so is a pointer that
+  // opaque() moved into vector registers.  The reads stay where a substep consumes them either way.
+  auto row = [&]() ABRK_LAMBDA {
+    long bb = b;
+    opaque(bb);
+    return bb;
+  };
+  auto get_u = [&](T(&u)[N]) ABRK_LAMBDA { load_row<N>(ug, row(), u); };
+  auto get_ext = [&](T(&e)[N]) ABRK_LAMBDA { load_row<N>(extg ? extg : ug, row(), e); };
+  auto get_w = [&](T(&w)[6]) ABRK_LAMBDA {
+    const T* wp = wg ? wg + row() * 6 : ug + row() * N;
+    const int step = wg ? 1 : 0;  // without a wrench: six reads of u[b, 0]
+    sfor<6>([&](auto k) ABRK_LAMBDA { w[k()] = wp[k() * step]; });
+  };
+  T minpiv = T(1);
+  const bool integrate = P.mode != 0;
+  plant_fx_row<A, T>(arm, P.h, integrate ? P.substeps : 1, P.gravity != 0, integrate, fxc, q, dq, get_u, get_ext, get_w,
+                     park, ddq, minpiv, scr);
+  if (integrate) {
+    store_row<N>(qg, row(), q);
+    store_row<N>(dqg, row(), dq);
+  } else {
+    store_row<N>(ddqg, row(), ddq);
+  }
+  if (any_lane(!(minpiv > T(0))) && P.status) *P.status = 1;
+}
+
 // ---- OSC._Mx / ._velocity_limiting / ._calc_orientation_forces for B rows (osc.py:120-215)
 template <int N, class T>
 ABRK_INL void mx_body(long b, int k, T thr, const T* __restrict__ Mg, const T* __restrict__ Jg, T* __restrict__ Mxg,

@@ -551,24 +551,42 @@ def twolink_step(plant, q, dq, u, dtype=np.float64, device=0, stream=None):
     check(lib().abrk_twolink_step_batch(a.code, C.byref(plant), B, qp, dqp, up, device, _sp(stream)))
 
 
-def forward_dynamics(arm_id, n, q, dq, u, ddq=None, dtype=np.float64, device=0, stream=None):
-    """ddq = M(q)^-1 (u - C(q,dq) dq - g(q)) for B states: q, dq, u [B,n] -> ddq [B,n]."""
+def forward_dynamics(arm_id, n, q, dq, u, ddq=None, dtype=np.float64, device=0, stream=None, effects=None,
+                     tau_ext=None, wrench=None):
+    """ddq = M(q)^-1 (tau - C(q,dq) dq - g(q)) for B states: q, dq, u [B,n] -> ddq [B,n].  tau = u, or with `effects`
+    (_abi.make_plant_effects), `tau_ext` [B,n], `wrench` [B,6]: the saturated u plus the loads and the friction
+    (include/abrk.h, abrk_plant_effects).  With all three None this is the plain entry point."""
     a = _Args(dtype)
     B = q.shape[0]
     qp, dqp, up = a.inp(q, (B, n), "q"), a.inp(dq, (B, n), "dq"), a.inp(u, (B, n), "u")
+    if effects is None and tau_ext is None and wrench is None:
+        op, oo = a.out(ddq, (B, n), device, "ddq")
+        check(lib().abrk_forward_dynamics_batch(arm_id, a.code, B, qp, dqp, up, op, device, _sp(stream)))
+        return oo
+    ep, wp = a.inp(tau_ext, (B, n), "tau_ext"), a.inp(wrench, (B, 6), "wrench")
     op, oo = a.out(ddq, (B, n), device, "ddq")
-    check(lib().abrk_forward_dynamics_batch(arm_id, a.code, B, qp, dqp, up, op, device, _sp(stream)))
+    check(lib().abrk_forward_dynamics_fx_batch(arm_id, a.code, None if effects is None else C.byref(effects), B, qp,
+                                               dqp, up, ep, wp, op, device, _sp(stream)))
     return oo
 
 
-def plant_step(arm_id, n, params, q, dq, u, dtype=np.float64, device=0, stream=None):
+def plant_step(arm_id, n, params, q, dq, u, dtype=np.float64, device=0, stream=None, effects=None, tau_ext=None,
+               wrench=None):
     """Rigid-body plant of any arm: (q, dq) [B,n] advanced in place by params.dt (_abi.make_plant_params) under the
-    torques u [B,n]."""
+    torques u [B,n].  `effects` (_abi.make_plant_effects: joint friction, limits, torque saturation), `tau_ext` [B,n] (a
+    joint-space disturbance) and `wrench` [B,6] (a world-frame wrench at the end effector) make the plant non-ideal
+    (include/abrk.h, abrk_plant_effects); with all three None this is the plain entry point.  Recorded into a plan, the
+    contents of tau_ext and wrench are read at every replay."""
     a = _Args(dtype)
     B = q.shape[0]
     qp, dqp = _inout(a, q, (B, n), "q"), _inout(a, dq, (B, n), "dq")
     up = a.inp(u, (B, n), "u")
-    check(lib().abrk_plant_step_batch(arm_id, a.code, C.byref(params), B, qp, dqp, up, device, _sp(stream)))
+    if effects is None and tau_ext is None and wrench is None:
+        check(lib().abrk_plant_step_batch(arm_id, a.code, C.byref(params), B, qp, dqp, up, device, _sp(stream)))
+        return
+    ep, wp = a.inp(tau_ext, (B, n), "tau_ext"), a.inp(wrench, (B, 6), "wrench")
+    check(lib().abrk_plant_step_fx_batch(arm_id, a.code, C.byref(params), None if effects is None else C.byref(effects),
+                                         B, qp, dqp, up, ep, wp, device, _sp(stream)))
 
 
 def osc_rollout_twolink(arm_id, params, plant, q, dq, target, n_steps, every=0, integrated_error=None,

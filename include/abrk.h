@@ -336,7 +336,8 @@ int abrk_osc_rollout_twolink_batch(int arm_id, int dtype, const abrk_osc_params*
  *   ddq = M(q)^-1 (u - C(q,dq) dq - g(q))      with M, C, g as robot_config.M / .C / .g return them
  *   `substeps` times, h = dt / substeps, u held:  dq += ddq h;  q += dq h     (the update order of
  *   abr_control/arms/twojoint/arm_sim.py:131-132; arms/threejoint/arm_sim.py:93-94 takes dt/1e-5 such substeps)
- * gravity = 0 leaves g out.  No joint friction, joint limits or contacts.
+ * gravity = 0 leaves g out.  These two entry points are the nominal plant; joint friction, joint limits, torque
+ * saturation and external loads are the *_fx entry points below.  No contacts.
  * A row whose M has a non-positive Cholesky pivot is reported as ABRK_ESINGULAR exactly as by
  * abrk_osc_generate_batch: host arrays - the call returns the code; device pointers - the stream's next sync does.
  * --------------------------------------------------------------------------------- */
@@ -352,6 +353,53 @@ int abrk_forward_dynamics_batch(int arm_id, int dtype, int64_t B, const void* q,
 /* (q, dq) [B,n] advanced in place by params->dt under the torques u [B,n] (host arrays: staged in and out). */
 int abrk_plant_step_batch(int arm_id, int dtype, const abrk_plant_params* params, int64_t B,
                           void* q, void* dq, const void* u, int device, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * The same plant with non-ideal effects, each of them optional.  Per substep of h = dt / substeps, with q and dq as
+ * they are at the start of the substep (n = the arm's joint count):
+ *   1. actuator saturation   tau_i  = clamp(u_i, -tau_max_i, +tau_max_i)
+ *   2. loads and friction    tau_i += tau_ext[b, i]                             per-row joint-space disturbance [B,n]
+ *                            tau_i += (J("EE", q)^T w[b])_i                     per-row wrench w = [fx fy fz mx my mz]
+ *                                     [B,6] in the world frame, applied at the origin of the end-effector frame (the
+ *                                     point Tx("EE", q) returns); J is the 6 x n Jacobian of robot_config.J("EE", q)
+ *                            tau_i -= damping_i dq_i                            viscous friction
+ *                            tau_i -= coulomb_i dq_i / sqrt(dq_i^2 + coulomb_vs^2)   Coulomb friction, smoothed
+ *   3. dynamics              ddq = M^-1 (tau - C dq - g)                        gravity = 0 leaves g out
+ *   4. integration           dq += ddq h;  q += dq h
+ *   5. joint limits          q_i > q_max_i: q_i = q_max_i, and dq_i > 0 becomes -restitution dq_i; the mirror image at
+ *                            q_min_i.  restitution = 0 leaves dq_i = 0.
+ * abrk_forward_dynamics_fx_batch does steps 1-3 once and returns ddq.  An effect whose flag is off needs no infinity
+ * in its fields (a zeroed struct will do: they only have to be finite); with fx, tau_ext and wrench all NULL, or with
+ * every flag off, the results have the bits of the plain entry points.  One set of per-joint constants serves every
+ * row.  ABRK_EINVAL (with a message): a negative damping or coulomb, coulomb_vs <= 0 with Coulomb friction on,
+ * tau_max <= 0 with saturation on, q_min >= q_max with limits on, restitution outside [0, 1], a non-finite value
+ * anywhere.  ABRK_ESINGULAR as above.  Recordable into a plan like every entry point: the kernel reads tau_ext and
+ * wrench where a substep consumes them, so their contents may change between replays.
+ * --------------------------------------------------------------------------------- */
+enum {
+  ABRK_FX_SATURATION = 1 << 0, /* tau_max                      */
+  ABRK_FX_VISCOUS = 1 << 1,    /* damping                      */
+  ABRK_FX_COULOMB = 1 << 2,    /* coulomb, coulomb_vs          */
+  ABRK_FX_LIMITS = 1 << 3      /* q_min, q_max, restitution    */
+};
+typedef struct abrk_plant_effects {
+  uint32_t flags; /* ABRK_FX_* */
+  double damping[ABRK_MAX_JOINTS]; /* >= 0 */
+  double coulomb[ABRK_MAX_JOINTS]; /* >= 0 */
+  double coulomb_vs;               /* > 0: the speed below which Coulomb friction fades to zero */
+  double tau_max[ABRK_MAX_JOINTS]; /* > 0 */
+  double q_min[ABRK_MAX_JOINTS];
+  double q_max[ABRK_MAX_JOINTS];   /* > q_min */
+  double restitution;              /* in [0, 1] */
+} abrk_plant_effects;
+
+/* fx, tau_ext [B,n] and wrench [B,6] may each be NULL */
+int abrk_forward_dynamics_fx_batch(int arm_id, int dtype, const abrk_plant_effects* fx, int64_t B, const void* q,
+                                   const void* dq, const void* u, const void* tau_ext, const void* wrench, void* ddq,
+                                   int device, void* stream);
+int abrk_plant_step_fx_batch(int arm_id, int dtype, const abrk_plant_params* params, const abrk_plant_effects* fx,
+                             int64_t B, void* q, void* dq, const void* u, const void* tau_ext, const void* wrench,
+                             int device, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Iterative inverse kinematics: InverseKinematics.generate_path

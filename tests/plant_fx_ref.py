@@ -1,0 +1,119 @@
+"""Reference of the plant with non-ideal effects (include/abrk.h, abrk_plant_effects), restated in NumPy on the oracle's
+M, C, g and J("EE", q) (general-inertia arms: the host build of the dynamics row program, tests/test_plant_hostsim.py
+HostsimGiDyn; their kinematics are the oracle's).  Per substep of h = dt / substeps:
+  1. tau = clamp(u, -tau_max, +tau_max)
+  2. tau += tau_ext + J^T w - damping dq - coulomb dq / sqrt(dq^2 + vs^2)        (q, dq of the substep's start)
+  3. ddq = solve(M, tau - C dq - g)
+  4. dq += ddq h; q += dq h
+  5. q beyond a limit: q = the limit, and a dq that points outwards becomes -restitution dq
+Shared by the CPU and the GPU tests.  The reference is fed inputs and constants already rounded to the dtype under test
+(rounded())."""
+import numpy as np
+
+from abr_control_amd import _abi
+from oracle.oracle import Oracle
+from tests.plant_ref import TOL_F32, TOL_F64, OracleDyn, rel_err  # noqa: F401  (re-exported to the tests)
+
+# the effects of the issue's cases, on every joint
+ALL_ON = dict(damping=0.5, coulomb=0.3, coulomb_vs=0.01, tau_max=12.0, q_min=-2.0, q_max=2.0, restitution=0.5)
+BAND = {np.dtype(np.float64): 1e-10, np.dtype(np.float32): 1e-6}   # pre-clamp |q - limit| below which a row is left out
+CAP = {np.dtype(np.float64): 0, np.dtype(np.float32): 1}          # ... and how many rows a case may leave out
+
+
+def draw(seed, B, n):
+    """-> q, dq, u, tau_ext, wrench: the fixed generator of the effects tests.  Every fifth row is put 0.2 - 1.8 mm inside
+    a limit of +-2 rad on one joint and sent outwards at 1 - 2 rad/s, so that it crosses within one 1 ms step."""
+    r = np.random.RandomState(seed)
+    q = r.uniform(-1.9, 1.9, (B, n))
+    dq = r.uniform(-2, 2, (B, n))
+    u = r.uniform(-20, 20, (B, n))
+    tau_ext = r.uniform(-5, 5, (B, n))
+    wrench = r.uniform(-10, 10, (B, 6))
+    d = r.uniform(2e-4, 1.8e-3, B)
+    v = r.uniform(1, 2, B)
+    for b in range(0, B, 5):
+        k = b // 5
+        j = k % n
+        s = 1.0 if k % 2 == 0 else -1.0
+        q[b, j] = s * (2.0 - d[b])
+        dq[b, j] = s * v[b]
+    return q, dq, u, tau_ext, wrench
+
+
+def rounded(dtype, *arrays):
+    """the arrays as the kernel sees them: rounded to `dtype`, held in float64"""
+    return tuple(None if a is None else np.asarray(a, dtype=dtype).astype(np.float64) for a in arrays)
+
+
+def effects_struct(n, fx):
+    """the C struct of an effects dict (None: no struct)"""
+    return None if fx is None else _abi.make_plant_effects(n, **fx)
+
+
+def effects_rounded(dtype, fx):
+    """an effects dict with its values rounded to `dtype`"""
+    if fx is None:
+        return None
+    return {k: (None if v is None else float(np.asarray(v, dtype=dtype))) for k, v in fx.items()}
+
+
+class RefFx:
+    """dyn: an object with mcg(q, dq) -> M, C, g (tests/plant_ref.py OracleDyn, HostsimGiDyn); table: the arm's table,
+    whose kinematics give J("EE", q)"""
+
+    def __init__(self, dyn, table):
+        self.dyn = dyn.mcg
+        self.O = dyn.O if hasattr(dyn, "O") else Oracle(table)
+
+    def tau(self, q, dq, u, fx=None, tau_ext=None, wrench=None):
+        """steps 1 and 2 for one row"""
+        fx = fx or {}
+        tau = np.array(u, dtype=np.float64)
+        if fx.get("tau_max") is not None:
+            tau = np.clip(tau, -fx["tau_max"], fx["tau_max"])
+        if tau_ext is not None:
+            tau = tau + tau_ext
+        if wrench is not None:
+            tau = tau + self.O.J("EE", q).T @ wrench
+        if fx.get("damping") is not None:
+            tau = tau - fx["damping"] * dq
+        if fx.get("coulomb") is not None:
+            tau = tau - fx["coulomb"] * dq / np.sqrt(dq * dq + fx["coulomb_vs"] ** 2)
+        return tau
+
+    def ddq(self, q, dq, u, fx=None, tau_ext=None, wrench=None, gravity=True):
+        out = np.empty_like(q)
+        for b in range(q.shape[0]):
+            M, Cm, g = self.dyn(q[b], dq[b])
+            tau = self.tau(q[b], dq[b], u[b], fx, None if tau_ext is None else tau_ext[b],
+                           None if wrench is None else wrench[b])
+            out[b] = np.linalg.solve(M, tau - Cm @ dq[b] - (g if gravity else 0.0))
+        return out
+
+    def steps(self, q, dq, u, dt, substeps=1, n_steps=1, fx=None, tau_ext=None, wrench=None, gravity=True,
+              band=0.0, after_step=None):
+        """-> q, dq, near [B] bool, crossings.  near: rows where some pre-clamp |q_i - limit| fell below `band` in some
+        substep (their decision may go either way in another arithmetic); crossings: limit events over all rows and
+        substeps.  after_step(q, dq) is called after every step of dt."""
+        q, dq = q.copy(), dq.copy()
+        h = dt / substeps
+        fx = fx or {}
+        limits = fx.get("q_min") is not None
+        near = np.zeros(q.shape[0], dtype=bool)
+        crossings = 0
+        for _ in range(n_steps):
+            for _ in range(substeps):
+                dq += self.ddq(q, dq, u, fx, tau_ext, wrench, gravity) * h
+                q += dq * h
+                if limits:
+                    lo, hi, e = fx["q_min"], fx["q_max"], fx["restitution"]
+                    near |= (np.minimum(np.abs(q - lo), np.abs(q - hi)) < band).any(axis=1)
+                    above, below = q > hi, q < lo
+                    crossings += int(above.sum() + below.sum())
+                    q[above] = hi
+                    q[below] = lo
+                    out = (above & (dq > 0)) | (below & (dq < 0))
+                    dq[out] = -e * dq[out]
+            if after_step is not None:
+                after_step(q, dq)
+        return q, dq, near, crossings

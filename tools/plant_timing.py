@@ -7,6 +7,14 @@ HIP events on the launch stream, 12 warm-up and 30 timed launches per figure; pr
   tick_graph_us                 the recorded {OSC cfg4; plant step} tick at 4096 rows, launch_graph(2000), per tick
 
     python tools/plant_timing.py [--rows-large 8388608]
+
+--effects: the plant with non-ideal effects against the plain step, in one process (profiles/plant_step.md): UR5 and
+Jaco2 fp64 at 4096 and 1 M rows, one step of 1 ms - plain entry point, effects entry point with nothing switched on,
+and with everything on (saturation, tau_ext, wrench, viscous and Coulomb friction, limits).  The three are timed in turn,
+five rounds of 12 warm-up + 30 timed launches each; the figure is the median over all 150 launches, the ratio is to the
+plain step of the same rounds.  Prints ONE JSON line.
+
+    python tools/plant_timing.py --effects [--rows-fx 1048576]
 """
 import argparse
 import json
@@ -20,10 +28,75 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 WARMUP, TIMED = 12, 30
 
 
+def effects_leg(rows_large):
+    import abr_control_amd as a
+    from abr_control_amd import _abi, engine
+    from abr_control_amd.arms import jaco2, ur5
+
+    s = a.Stream(0)
+    p = _abi.make_plant_params(1e-3)
+    res = {"leg": "effects", "dtype": "float64", "device": a.device_name(0), "warmup": WARMUP, "timed": TIMED,
+           "rounds": 5, "us": {}}
+    e0, e1 = a.Event(0), a.Event(0)
+
+    def one_round(fn):
+        for _ in range(WARMUP):
+            fn()
+        s.sync()
+        ts = []
+        for _ in range(TIMED):
+            e0.record(s)
+            fn()
+            e1.record(s)
+            s.sync()
+            ts.append(e1.elapsed_ms_since(e0) * 1e3)
+        return ts
+
+    for name, rc in (("ur5", ur5.Config()), ("jaco2", jaco2.Config())):
+        n = rc.N_JOINTS
+        all_on = _abi.make_plant_effects(n, damping=0.5, coulomb=0.3, coulomb_vs=0.01, tau_max=12.0, q_min=-2.0,
+                                         q_max=2.0, restitution=0.5)
+        all_off = _abi.make_plant_effects(n)
+        res["us"][name] = {}
+        for B in (4096, rows_large):
+            rng = np.random.RandomState(0)
+            q0, dq0 = rng.uniform(-1.9, 1.9, (B, n)), rng.uniform(-2, 2, (B, n))
+            u, ext, w = (a.DeviceArray.from_numpy(x) for x in (rng.uniform(-20, 20, (B, n)), rng.uniform(-5, 5, (B, n)),
+                                                               rng.uniform(-10, 10, (B, 6))))
+            q, dq = a.DeviceArray.from_numpy(q0), a.DeviceArray.from_numpy(dq0)
+
+            def reset():  # every round starts from the same state: the three forms see the same rows
+                q.copy_from_numpy(q0, stream=s)
+                dq.copy_from_numpy(dq0, stream=s)
+                s.sync()
+
+            forms = {
+                "plain": lambda: engine.plant_step(rc.arm_id, n, p, q, dq, u, stream=s),
+                "fx_all_off": lambda: engine.plant_step(rc.arm_id, n, p, q, dq, u, stream=s, effects=all_off),
+                "fx_all_on": lambda: engine.plant_step(rc.arm_id, n, p, q, dq, u, stream=s, effects=all_on, tau_ext=ext,
+                                                       wrench=w),
+            }
+            ts = {k: [] for k in forms}
+            for _ in range(res["rounds"]):
+                for k, fn in forms.items():
+                    reset()
+                    ts[k] += one_round(fn)
+            out = {k: {"median_us": float(np.median(v)), "min_us": float(np.min(v)), "max_us": float(np.max(v))}
+                   for k, v in ts.items()}
+            for k in ("fx_all_off", "fx_all_on"):
+                out[k]["ratio_to_plain"] = out[k]["median_us"] / out["plain"]["median_us"]
+            res["us"][name][str(B)] = out
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows-large", type=int, default=8 << 20)
+    ap.add_argument("--effects", action="store_true", help="time the plant with effects against the plain step")
+    ap.add_argument("--rows-fx", type=int, default=1 << 20)
     args = ap.parse_args()
+    if args.effects:
+        return effects_leg(args.rows_fx)
     import abr_control_amd as a
     from abr_control_amd import _abi, engine
     from abr_control_amd.arms import ur5
