@@ -61,6 +61,29 @@ static int fail(int code, const char* fmt, ...) {
     }                                                                                      \
   } while (0)
 
+// The sign and class of the double at `p`.  The library is built with -ffinite-math-only, under which the compiler
+// folds std::isfinite, NaN compares and even an exponent test of a value it knows to be a double: the bits are read
+// through an integer the optimiser is kept away from.
+struct F64Bits {
+  bool finite, negative, zero;
+};
+__attribute__((noinline, optnone)) static F64Bits f64_bits_at(const void* p) {
+  volatile uint64_t b;
+  memcpy(const_cast<uint64_t*>(&b), p, sizeof(uint64_t));
+  const uint64_t v = b;
+  return {((v >> 52) & 0x7ff) != 0x7ff, (v >> 63) != 0, (v << 1) == 0};
+}
+static bool finite_at(const void* p) { return f64_bits_at(p).finite; }
+static bool positive_finite_at(const void* p) {
+  const F64Bits b = f64_bits_at(p);
+  return b.finite && !b.negative && !b.zero;
+}
+// finite and >= 0 (a zero of either sign)
+static bool nonnegative_finite_at(const void* p) {
+  const F64Bits b = f64_bits_at(p);
+  return b.finite && (!b.negative || b.zero);
+}
+
 extern "C" const char* abrk_last_error(void) { return g_err.c_str(); }
 extern "C" int abrk_version(void) { return ABRK_VERSION; }
 
@@ -2022,7 +2045,7 @@ extern "C" int abrk_osc_rollout_twolink_batch(int arm_id, int dtype, const abrk_
   });
 }
 
-// ------------------------------------------------------------------------------- rigid-body plant of any arm
+// ------------------------------------------------------- rigid-body plant of any arm, plain and with non-ideal effects
 namespace {
 template <class T>
 PlantP<T> make_plantp(double h, int substeps, int gravity, int mode) {
@@ -2034,83 +2057,6 @@ PlantP<T> make_plantp(double h, int substeps, int gravity, int mode) {
   p.status = nullptr;
   return p;
 }
-// Is the double at `p` a finite number > 0?  The library is built with -ffinite-math-only, under which the compiler
-// folds std::isfinite, NaN compares and even an exponent test of a value it knows to be a double: the bits are read
-// through an integer the optimiser is kept away from.
-__attribute__((noinline, optnone)) bool positive_finite_at(const void* p) {
-  volatile uint64_t b;
-  memcpy(const_cast<uint64_t*>(&b), p, sizeof(uint64_t));
-  const uint64_t v = b;
-  const bool finite = ((v >> 52) & 0x7ff) != 0x7ff, negative = (v >> 63) != 0, zero = (v << 1) == 0;
-  return finite && !negative && !zero;
-}
-// mode 0: ddq out, q / dq read; mode 1: q / dq in place
-int plant_impl(int arm_id, int dtype, int mode, double dt, int substeps, int gravity, int64_t B, void* q, void* dq,
-               const void* u, void* ddq, int device, void* stream) {
-  ArmEntry* a;
-  if (int rc = check_common(arm_id, dtype, B, &a)) return rc;
-  if (!a->ops->plant) return fail(ABRK_EINVAL, "this arm's kernels carry no plant (rebuild its plugin)");
-  if (!q || !dq || !u || (mode == 0 && !ddq)) return fail(ABRK_EINVAL, "q, dq, u%s are required", mode == 0 ? ", ddq" : "");
-  if (B == 0) return 0;
-  if (int rc = use_device(device)) return rc;
-  const int n = a->desc.n_joints;
-  const size_t bytes = (size_t)B * n * esz(dtype);
-  Stager st{device, (hipStream_t)stream};
-  PlantArgs pa{};
-  if (mode == 0) {
-    st.bind(&pa.q, q, bytes, true, false);
-    st.bind(&pa.dq, dq, bytes, true, false);
-  } else {
-    st.inout(&pa.q, q, bytes);
-    st.inout(&pa.dq, dq, bytes);
-  }
-  st.in(&pa.u, u, bytes);
-  st.out(&pa.ddq, mode == 0 ? ddq : nullptr, bytes);
-  if (int rc = st.reserve()) return rc;
-  auto pb = blocks([&](auto t) { return make_plantp<decltype(t)>(dt / substeps, substeps, gravity, mode); });
-  const ArmOps* ops = a->ops;
-  const hipStream_t hs = (hipStream_t)stream;
-  return with_status_word(st, pb, nullptr, [&] {
-    return dispatch(st, a, dtype, [=](const void* rt) {
-      PlantArgs o = pa;
-      o.P = pb.of(dtype);
-      return ops->plant(dtype, LaunchArgs{rt, (long)B, hs}, o);
-    });
-  });
-}
-}  // namespace
-
-extern "C" int abrk_forward_dynamics_batch(int arm_id, int dtype, int64_t B, const void* q, const void* dq,
-                                           const void* u, void* ddq, int device, void* stream) {
-  return plant_impl(arm_id, dtype, 0, 1.0, 1, 1, B, const_cast<void*>(q), const_cast<void*>(dq), u, ddq, device, stream);
-}
-
-extern "C" int abrk_plant_step_batch(int arm_id, int dtype, const abrk_plant_params* P, int64_t B, void* q, void* dq,
-                                     const void* u, int device, void* stream) {
-  if (!get_arm(arm_id)) return fail(ABRK_ENOARM, "unknown arm id %d", arm_id);
-  if (!P) return fail(ABRK_EINVAL, "params is NULL");
-  if (!positive_finite_at(&P->dt)) return fail(ABRK_EINVAL, "dt=%g is not a positive finite step", P->dt);
-  if (P->substeps < 1) return fail(ABRK_EINVAL, "substeps=%d < 1", P->substeps);
-  return plant_impl(arm_id, dtype, 1, P->dt, P->substeps, P->gravity ? 1 : 0, B, q, dq, u, nullptr, device, stream);
-}
-
-// ------------------------------------------------------------------------------- the plant with non-ideal effects
-namespace {
-static_assert((int)PlantFxP<double>::kJ == ABRK_MAX_JOINTS, "PlantFxP holds one constant per joint and effect");
-// Is the double at `p` finite?  On its bits, like positive_finite_at.
-__attribute__((noinline, optnone)) bool fx_finite_at(const void* p) {
-  volatile uint64_t b;
-  memcpy(const_cast<uint64_t*>(&b), p, sizeof(uint64_t));
-  const uint64_t v = b;
-  return ((v >> 52) & 0x7ff) != 0x7ff;
-}
-// finite and >= 0 (a zero of either sign)
-__attribute__((noinline, optnone)) bool fx_nonnegative_at(const void* p) {
-  volatile uint64_t b;
-  memcpy(const_cast<uint64_t*>(&b), p, sizeof(uint64_t));
-  const uint64_t v = b;
-  return ((v >> 52) & 0x7ff) != 0x7ff && ((v >> 63) == 0 || (v << 1) == 0);
-}
 // Every field of the arm's n joints must be finite whether its effect is on or not (a zeroed struct is); the sign and
 // order rules of tau_max, coulomb_vs and the limits hold where their flag puts them to use.
 int check_effects(const abrk_plant_effects* fx, int n) {
@@ -2118,52 +2064,42 @@ int check_effects(const abrk_plant_effects* fx, int n) {
   const uint32_t all = ABRK_FX_SATURATION | ABRK_FX_VISCOUS | ABRK_FX_COULOMB | ABRK_FX_LIMITS;
   if (fx->flags & ~all) return fail(ABRK_EINVAL, "effects: flags=0x%x has bits beyond ABRK_FX_*", fx->flags);
   for (int i = 0; i < n; i++) {
-    if (!fx_nonnegative_at(&fx->damping[i]))
+    if (!nonnegative_finite_at(&fx->damping[i]))
       return fail(ABRK_EINVAL, "effects: damping[%d]=%g is not a finite value >= 0", i, fx->damping[i]);
-    if (!fx_nonnegative_at(&fx->coulomb[i]))
+    if (!nonnegative_finite_at(&fx->coulomb[i]))
       return fail(ABRK_EINVAL, "effects: coulomb[%d]=%g is not a finite value >= 0", i, fx->coulomb[i]);
-    if (!fx_finite_at(&fx->tau_max[i]) || ((fx->flags & ABRK_FX_SATURATION) && !positive_finite_at(&fx->tau_max[i])))
+    if (!finite_at(&fx->tau_max[i]) || ((fx->flags & ABRK_FX_SATURATION) && !positive_finite_at(&fx->tau_max[i])))
       return fail(ABRK_EINVAL, "effects: tau_max[%d]=%g is not a finite value > 0", i, fx->tau_max[i]);
-    if (!fx_finite_at(&fx->q_min[i]) || !fx_finite_at(&fx->q_max[i]))
+    if (!finite_at(&fx->q_min[i]) || !finite_at(&fx->q_max[i]))
       return fail(ABRK_EINVAL, "effects: q_min[%d]=%g, q_max[%d]=%g: a limit is not finite", i, fx->q_min[i], i,
                   fx->q_max[i]);
     if ((fx->flags & ABRK_FX_LIMITS) && !(fx->q_min[i] < fx->q_max[i]))
       return fail(ABRK_EINVAL, "effects: q_min[%d]=%g is not below q_max[%d]=%g", i, fx->q_min[i], i, fx->q_max[i]);
   }
-  if (!fx_finite_at(&fx->coulomb_vs) || ((fx->flags & ABRK_FX_COULOMB) && !positive_finite_at(&fx->coulomb_vs)))
+  if (!finite_at(&fx->coulomb_vs) || ((fx->flags & ABRK_FX_COULOMB) && !positive_finite_at(&fx->coulomb_vs)))
     return fail(ABRK_EINVAL, "effects: coulomb_vs=%g is not a finite value > 0", fx->coulomb_vs);
-  if (!fx_nonnegative_at(&fx->restitution) || fx->restitution > 1.0)
+  if (!nonnegative_finite_at(&fx->restitution) || fx->restitution > 1.0)
     return fail(ABRK_EINVAL, "effects: restitution=%g is outside [0, 1]", fx->restitution);
   return 0;
 }
-// The kernel's constants (abrk_ctrl.h PlantFxP): an effect that is off becomes the value that leaves the row as it is,
-// since the row program takes no branch on the flags.
-template <class T>
-PlantFxP<T> make_plantfx(const abrk_plant_effects* fx, int n, bool have_ext, bool have_w) {
-  using F = PlantFxP<T>;
-  F f{};
-  const uint32_t flags = fx ? fx->flags : 0;
-  const T big = std::numeric_limits<T>::max();
-  for (int i = 0; i < n; i++) {
-    f.c[F::DAMP + i] = (flags & ABRK_FX_VISCOUS) ? T(fx->damping[i]) : T(0);
-    f.c[F::COUL + i] = (flags & ABRK_FX_COULOMB) ? T(fx->coulomb[i]) : T(0);
-    f.c[F::TMAX + i] = (flags & ABRK_FX_SATURATION) ? T(fx->tau_max[i]) : big;
-    f.c[F::QMIN + i] = (flags & ABRK_FX_LIMITS) ? T(fx->q_min[i]) : -big;
-    f.c[F::QMAX + i] = (flags & ABRK_FX_LIMITS) ? T(fx->q_max[i]) : big;
-  }
-  f.c[F::VS2] = (flags & ABRK_FX_COULOMB) ? T(fx->coulomb_vs) * T(fx->coulomb_vs) : T(1);
-  f.c[F::REST] = (flags & ABRK_FX_LIMITS) ? T(fx->restitution) : T(0);
-  f.c[F::ON_EXT] = have_ext ? T(1) : T(0);
-  f.c[F::ON_W] = have_w ? T(1) : T(0);
-  return f;
+// the checks of the two step entries, ahead of plant_impl's own
+int check_plant_params(int arm_id, const abrk_plant_params* P) {
+  if (!get_arm(arm_id)) return fail(ABRK_ENOARM, "unknown arm id %d", arm_id);
+  if (!P) return fail(ABRK_EINVAL, "params is NULL");
+  if (!positive_finite_at(&P->dt)) return fail(ABRK_EINVAL, "dt=%g is not a positive finite step", P->dt);
+  if (P->substeps < 1) return fail(ABRK_EINVAL, "substeps=%d < 1", P->substeps);
+  return 0;
 }
-// plant_impl with the effects block and the two optional load arrays
-int plant_fx_impl(int arm_id, int dtype, int mode, double dt, int substeps, int gravity, const abrk_plant_effects* fx,
-                  int64_t B, void* q, void* dq, const void* u, const void* tau_ext, const void* wrench, void* ddq,
-                  int device, void* stream) {
+// mode 0: ddq out, q / dq read; mode 1: q / dq in place.  fx_entry: the entries with non-ideal effects, which launch the
+// effects kernel whatever is switched on; the others launch the plain kernel and pass no fx, tau_ext or wrench.
+int plant_impl(bool fx_entry, int arm_id, int dtype, int mode, double dt, int substeps, int gravity,
+               const abrk_plant_effects* fx, int64_t B, void* q, void* dq, const void* u, const void* tau_ext,
+               const void* wrench, void* ddq, int device, void* stream) {
   ArmEntry* a;
   if (int rc = check_common(arm_id, dtype, B, &a)) return rc;
-  if (!a->ops->plant_fx) return fail(ABRK_EINVAL, "this arm's kernels carry no plant with effects (rebuild its plugin)");
+  if (!fx_entry && !a->ops->plant) return fail(ABRK_EINVAL, "this arm's kernels carry no plant (rebuild its plugin)");
+  if (fx_entry && !a->ops->plant_fx)
+    return fail(ABRK_EINVAL, "this arm's kernels carry no plant with effects (rebuild its plugin)");
   if (!q || !dq || !u || (mode == 0 && !ddq)) return fail(ABRK_EINVAL, "q, dq, u%s are required", mode == 0 ? ", ddq" : "");
   const int n = a->desc.n_joints;
   if (int rc = check_effects(fx, n)) return rc;
@@ -2171,7 +2107,7 @@ int plant_fx_impl(int arm_id, int dtype, int mode, double dt, int substeps, int 
   if (int rc = use_device(device)) return rc;
   const size_t bytes = (size_t)B * n * esz(dtype);
   Stager st{device, (hipStream_t)stream};
-  PlantFxArgs pa{};
+  PlantFxArgs pa{};  // (the plain kernel's PlantArgs: its q, dq, u and ddq)
   if (mode == 0) {
     st.bind(&pa.q, q, bytes, true, false);
     st.bind(&pa.dq, dq, bytes, true, false);
@@ -2185,10 +2121,14 @@ int plant_fx_impl(int arm_id, int dtype, int mode, double dt, int substeps, int 
   st.out(&pa.ddq, mode == 0 ? ddq : nullptr, bytes);
   if (int rc = st.reserve()) return rc;
   auto pb = blocks([&](auto t) { return make_plantp<decltype(t)>(dt / substeps, substeps, gravity, mode); });
-  const auto fb = blocks([&](auto t) { return make_plantfx<decltype(t)>(fx, n, tau_ext != nullptr, wrench != nullptr); });
   const ArmOps* ops = a->ops;
   const hipStream_t hs = (hipStream_t)stream;
   return with_status_word(st, pb, nullptr, [&] {
+    if (!fx_entry)
+      return dispatch(st, a, dtype, [=](const void* rt) {
+        return ops->plant(dtype, LaunchArgs{rt, (long)B, hs}, PlantArgs{pb.of(dtype), pa.q, pa.dq, pa.u, pa.ddq});
+      });
+    const auto fb = blocks([&](auto t) { return make_plantfx<decltype(t)>(fx, n, tau_ext != nullptr, wrench != nullptr); });
     return dispatch(st, a, dtype, [=](const void* rt) {
       PlantFxArgs o = pa;
       o.P = pb.of(dtype);
@@ -2199,22 +2139,32 @@ int plant_fx_impl(int arm_id, int dtype, int mode, double dt, int substeps, int 
 }
 }  // namespace
 
+extern "C" int abrk_forward_dynamics_batch(int arm_id, int dtype, int64_t B, const void* q, const void* dq,
+                                           const void* u, void* ddq, int device, void* stream) {
+  return plant_impl(false, arm_id, dtype, 0, 1.0, 1, 1, nullptr, B, const_cast<void*>(q), const_cast<void*>(dq), u,
+                    nullptr, nullptr, ddq, device, stream);
+}
+
+extern "C" int abrk_plant_step_batch(int arm_id, int dtype, const abrk_plant_params* P, int64_t B, void* q, void* dq,
+                                     const void* u, int device, void* stream) {
+  if (int rc = check_plant_params(arm_id, P)) return rc;
+  return plant_impl(false, arm_id, dtype, 1, P->dt, P->substeps, P->gravity ? 1 : 0, nullptr, B, q, dq, u, nullptr,
+                    nullptr, nullptr, device, stream);
+}
+
 extern "C" int abrk_forward_dynamics_fx_batch(int arm_id, int dtype, const abrk_plant_effects* fx, int64_t B,
                                               const void* q, const void* dq, const void* u, const void* tau_ext,
                                               const void* wrench, void* ddq, int device, void* stream) {
-  return plant_fx_impl(arm_id, dtype, 0, 1.0, 1, 1, fx, B, const_cast<void*>(q), const_cast<void*>(dq), u, tau_ext,
-                       wrench, ddq, device, stream);
+  return plant_impl(true, arm_id, dtype, 0, 1.0, 1, 1, fx, B, const_cast<void*>(q), const_cast<void*>(dq), u, tau_ext,
+                    wrench, ddq, device, stream);
 }
 
 extern "C" int abrk_plant_step_fx_batch(int arm_id, int dtype, const abrk_plant_params* P, const abrk_plant_effects* fx,
                                         int64_t B, void* q, void* dq, const void* u, const void* tau_ext,
                                         const void* wrench, int device, void* stream) {
-  if (!get_arm(arm_id)) return fail(ABRK_ENOARM, "unknown arm id %d", arm_id);
-  if (!P) return fail(ABRK_EINVAL, "params is NULL");
-  if (!positive_finite_at(&P->dt)) return fail(ABRK_EINVAL, "dt=%g is not a positive finite step", P->dt);
-  if (P->substeps < 1) return fail(ABRK_EINVAL, "substeps=%d < 1", P->substeps);
-  return plant_fx_impl(arm_id, dtype, 1, P->dt, P->substeps, P->gravity ? 1 : 0, fx, B, q, dq, u, tau_ext, wrench,
-                       nullptr, device, stream);
+  if (int rc = check_plant_params(arm_id, P)) return rc;
+  return plant_impl(true, arm_id, dtype, 1, P->dt, P->substeps, P->gravity ? 1 : 0, fx, B, q, dq, u, tau_ext, wrench,
+                    nullptr, device, stream);
 }
 
 // ------------------------------------------------------------------------------- loop recorder
@@ -2223,13 +2173,6 @@ static_assert((unsigned)ABRK_TR_Q == (unsigned)TR_Q && (unsigned)ABRK_TR_DQ == (
                   (unsigned)ABRK_TR_U == (unsigned)TR_U && (unsigned)ABRK_TR_TARGET == (unsigned)TR_TARGET &&
                   (unsigned)ABRK_TR_XYZ == (unsigned)TR_XYZ && (unsigned)ABRK_TR_ERR == (unsigned)TR_ERR,
               "abrk_types.h and abrk_trace.h name the same columns");
-// Is the double at `p` finite?  On its bits, like positive_finite_at.
-__attribute__((noinline, optnone)) bool finite_at(const void* p) {
-  volatile uint64_t b;
-  memcpy(const_cast<uint64_t*>(&b), p, sizeof(uint64_t));
-  const uint64_t v = b;
-  return ((v >> 52) & 0x7ff) != 0x7ff;
-}
 template <class T>
 TraceP<T> make_tracep(const abrk_trace_params& P, int n) {
   TraceP<T> p;

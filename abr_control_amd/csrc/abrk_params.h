@@ -1,7 +1,9 @@
 // abrk_params.h - host-side conversion of the C ABI parameter structs (include/abrk.h) into the
-// typed blocks the row programs consume.  Shared by abrk_host.cpp and tests/hostsim.
+// typed blocks the row programs consume.  Shared by abrk_host.cpp, tests/hostsim and tests/hostsim_plant.
 #pragma once
+#include <cstdint>
 #include <cstring>
+#include <limits>
 
 #include "../../include/abrk.h"
 #include "abrk_ctrl.h"
@@ -106,6 +108,29 @@ inline ObsP<T> make_obsp(const abrk_obstacles_params& s) {
   for (int i = 0; i < s.n_obstacles && i < 16; i++)
     for (int r = 0; r < 4; r++) p.obs[i][r] = T(s.obstacles[i][r]);
   return p;
+}
+
+// The constants of the plant with non-ideal effects (abrk_ctrl.h PlantFxP): an effect that is off becomes the value that
+// leaves the row as it is, since the row program takes no branch on the flags.
+static_assert((int)PlantFxP<double>::kJ == ABRK_MAX_JOINTS, "PlantFxP holds one constant per joint and effect");
+template <class T>
+PlantFxP<T> make_plantfx(const abrk_plant_effects* fx, int n, bool have_ext, bool have_w) {
+  using F = PlantFxP<T>;
+  F f{};
+  const uint32_t flags = fx ? fx->flags : 0;
+  const T big = std::numeric_limits<T>::max();
+  for (int i = 0; i < n; i++) {
+    f.c[F::DAMP + i] = (flags & ABRK_FX_VISCOUS) ? T(fx->damping[i]) : T(0);
+    f.c[F::COUL + i] = (flags & ABRK_FX_COULOMB) ? T(fx->coulomb[i]) : T(0);
+    f.c[F::TMAX + i] = (flags & ABRK_FX_SATURATION) ? T(fx->tau_max[i]) : big;
+    f.c[F::QMIN + i] = (flags & ABRK_FX_LIMITS) ? T(fx->q_min[i]) : -big;
+    f.c[F::QMAX + i] = (flags & ABRK_FX_LIMITS) ? T(fx->q_max[i]) : big;
+  }
+  f.c[F::VS2] = (flags & ABRK_FX_COULOMB) ? T(fx->coulomb_vs) * T(fx->coulomb_vs) : T(1);
+  f.c[F::REST] = (flags & ABRK_FX_LIMITS) ? T(fx->restitution) : T(0);
+  f.c[F::ON_EXT] = have_ext ? T(1) : T(0);
+  f.c[F::ON_W] = have_w ? T(1) : T(0);
+  return f;
 }
 
 // The FAST OSC kernels apply when the task rows are exactly the first k position rows of the end-effector:

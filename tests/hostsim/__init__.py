@@ -2,15 +2,14 @@
 abr_control_amd.engine, but runs the row programs on the CPU.  Never imported by the product."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
 from abr_control_amd import _abi
 from abr_control_amd.engine import _OUT_SHAPES, _WANT_BITS, _dtype_code
+from tests import hostsim_build
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "..", "..", "abr_control_amd", "csrc")
 # built in parts, in parallel (a single translation unit takes minutes)
 PARTS = {
     "static": ["-DHOSTSIM_STATIC=1"],
@@ -28,23 +27,9 @@ def _so(part):
 
 
 def build(force=False):
-    srcs = [os.path.join(_HERE, "hostsim.cpp")] + [
-        os.path.join(_CSRC, f)
-        for f in ("abrk_device.h", "abrk_ctrl.h", "abrk_rows.h", "abrk_params.h", "abrk_rt.h", "abrk_arms_builtin.h",
-                  "abrk_sincos_table.h", "abrk_osc6_plan.h")]
-    newest = max(os.path.getmtime(s) for s in srcs)
-    procs = []
-    for part, defs in PARTS.items():
-        so = _so(part)
-        if force or not os.path.exists(so) or os.path.getmtime(so) < newest:
-            procs.append(subprocess.Popen(
-                ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O1", "-std=c++17", "-fPIC", "-shared",
-                 "-fno-signed-zeros", "-ffinite-math-only", "--cuda-host-only", *defs, "-o", so, srcs[0]],
-                stdout=subprocess.DEVNULL, stderr=subprocess.PIPE))
-    for p in procs:
-        err = p.communicate()[1]
-        if p.returncode:
-            raise RuntimeError("hostsim build failed:\n" + err.decode()[-3000:])
+    deps = hostsim_build.csrc("abrk_device.h", "abrk_ctrl.h", "abrk_rows.h", "abrk_params.h", "abrk_rt.h",
+                              "abrk_arms_builtin.h", "abrk_sincos_table.h", "abrk_osc6_plan.h") + [hostsim_build.ABRK_H]
+    hostsim_build.build_many(os.path.join(_HERE, "hostsim.cpp"), deps, {_so(p): d for p, d in PARTS.items()}, force)
     return [_so(p) for p in PARTS]
 
 

@@ -1,49 +1,26 @@
 """Python side of the hostsim_gi TEST AID (tests/hostsim_gi/hostsim_gi.cpp): the row programs built for the host on a
 general-inertia arm table, one small library per table.  Never imported by the product."""
 import ctypes as C
-import hashlib
 import os
-import subprocess
 
 import numpy as np
 
-from abr_control_amd import _abi
 from abr_control_amd.engine import _OUT_SHAPES, _WANT_BITS
+from tests import hostsim_build
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "..", "..", "abr_control_amd", "csrc")
 _BUILD = os.path.join(_HERE, "build")
+_DEPS = hostsim_build.csrc("abrk_device.h", "abrk_ctrl.h", "abrk_rows.h", "abrk_arms_builtin.h", "abrk_sincos_table.h")
 _libs = {}
-
-
-def _sources():
-    return [os.path.join(_HERE, "hostsim_gi.cpp")] + [
-        os.path.join(_CSRC, f) for f in ("abrk_device.h", "abrk_ctrl.h", "abrk_rows.h", "abrk_arms_builtin.h",
-                                         "abrk_sincos_table.h")]
 
 
 def lib_for(table):
     """the host build of the row programs on `table` (built on first use, rebuilt when a source is newer)"""
-    src = _abi.render_tab_struct(table, "Tab_hostsim_gi")
-    key = hashlib.sha256(src.encode()).hexdigest()[:16]
-    if key in _libs:
-        return _libs[key]
-    os.makedirs(_BUILD, exist_ok=True)
-    hdr = os.path.join(_BUILD, f"tab_{key}.h")
-    so = os.path.join(_BUILD, f"libhostsim_gi_{key}.so")
-    with open(hdr + ".tmp", "w") as fh:
-        fh.write("#pragma once\nnamespace abrk {\n" + src + "\n}  // namespace abrk\n")
-    os.replace(hdr + ".tmp", hdr)
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in _sources()):
-        r = subprocess.run(
-            ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O1", "-std=c++17", "-fPIC", "-shared",
-             "-fno-signed-zeros", "-ffinite-math-only", "--cuda-host-only", "-include", hdr,
-             "-DHOSTSIM_GI_TAB=abrk::Tab_hostsim_gi", "-o", so + ".tmp", _sources()[0]],
-            capture_output=True, text=True)
-        if r.returncode:
-            raise RuntimeError("hostsim_gi build failed:\n" + r.stderr[-3000:])
-        os.replace(so + ".tmp", so)
-    _libs[key] = C.CDLL(so)
+    key, hdr = hostsim_build.table_header(_BUILD, table, "Tab_hostsim_gi")
+    if key not in _libs:
+        _libs[key] = C.CDLL(hostsim_build.build(
+            os.path.join(_HERE, "hostsim_gi.cpp"), os.path.join(_BUILD, f"libhostsim_gi_{key}.so"), _DEPS,
+            ["-include", hdr, "-DHOSTSIM_GI_TAB=abrk::Tab_hostsim_gi"]))
     return _libs[key]
 
 

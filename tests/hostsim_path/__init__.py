@@ -2,16 +2,14 @@
 built for the host on first use.  Never imported by the product."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
 from abr_control_amd import _abi
 from abr_control_amd.controllers.path_planners.path_planner import profile_tables
+from tests import hostsim_build
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "..", "..", "abr_control_amd", "csrc")
-_BUILD = os.path.join(_HERE, "build")
 _lib = None
 
 
@@ -19,18 +17,8 @@ def lib():
     global _lib
     if _lib is not None:
         return _lib
-    srcs = [os.path.join(_HERE, "hostsim_path.cpp"), os.path.join(_CSRC, "abrk_path.h")]
-    os.makedirs(_BUILD, exist_ok=True)
-    so = os.path.join(_BUILD, "libhostsim_path.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        tmp = f"{so}.{os.getpid()}.tmp"
-        r = subprocess.run(
-            ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O1", "-std=c++17", "-fPIC", "-shared",
-             "-fno-signed-zeros", "-ffinite-math-only", "--cuda-host-only", "-o", tmp, srcs[0]],
-            capture_output=True, text=True)
-        if r.returncode:
-            raise RuntimeError("hostsim_path build failed:\n" + r.stderr[-3000:])
-        os.replace(tmp, so)
+    so = hostsim_build.build(os.path.join(_HERE, "hostsim_path.cpp"),
+                             os.path.join(_HERE, "build", "libhostsim_path.so"), hostsim_build.csrc("abrk_path.h"))
     L = C.CDLL(so)
     head = [C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
     L.hostsim_path_plan.argtypes = head + [C.c_void_p] * 5

@@ -1,94 +1,83 @@
-"""Python side of the hostsim_plant TEST AID (tests/hostsim_plant/hostsim_plant.cpp): the plant row program built for the
-host, one small library per arm table (compile-time tables) or per joint count (runtime tables).  Never imported by the
-product."""
+"""Python side of the hostsim_plant TEST AID (tests/hostsim_plant/hostsim_plant.cpp): the plant's two row programs, the
+plain one and the one with non-ideal effects, built for the host side by side, one small library per arm table
+(compile-time tables) or per joint count (runtime tables).  plain_only=True: a build of its own that holds the plain row
+program alone.  Never imported by the product."""
 import ctypes as C
-import hashlib
 import os
-import subprocess
 
 import numpy as np
 
 from abr_control_amd import _abi
+from tests import hostsim_build
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "..", "..", "abr_control_amd", "csrc")
 _BUILD = os.path.join(_HERE, "build")
+_DEPS = hostsim_build.csrc("abrk_device.h", "abrk_ctrl.h", "abrk_rows.h", "abrk_kernels.h", "abrk_rt.h",
+                           "abrk_arms_builtin.h", "abrk_sincos_table.h", "abrk_params.h") + [hostsim_build.ABRK_H]
 _libs = {}
 
 
-def _sources():
-    return [os.path.join(_HERE, "hostsim_plant.cpp")] + [
-        os.path.join(_CSRC, f) for f in ("abrk_device.h", "abrk_ctrl.h", "abrk_rows.h", "abrk_kernels.h", "abrk_rt.h",
-                                         "abrk_arms_builtin.h", "abrk_sincos_table.h")]
+def _build(key, defs, plain_only):
+    if plain_only:
+        key, defs = key + "_plain", defs + ["-DHOSTSIM_PLANT_PLAIN_ONLY"]
+    if key not in _libs:
+        L = C.CDLL(hostsim_build.build(os.path.join(_HERE, "hostsim_plant.cpp"),
+                                       os.path.join(_BUILD, f"libhostsim_plant_{key}.so"), _DEPS, defs))
+        L.hostsim_plant.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
+                                    C.POINTER(_abi.PlantEffects), C.c_int64] + [C.c_void_p] * 6
+        _libs[key] = L
+    return _libs[key]
 
 
-def _build(key, flags):
-    if key in _libs:
-        return _libs[key]
-    os.makedirs(_BUILD, exist_ok=True)
-    so = os.path.join(_BUILD, f"libhostsim_plant_{key}.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in _sources()):
-        tmp = f"{so}.{os.getpid()}.tmp"
-        r = subprocess.run(
-            ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O1", "-std=c++17", "-fPIC", "-shared",
-             "-fno-signed-zeros", "-ffinite-math-only", "--cuda-host-only", *flags, "-o", tmp, _sources()[0]],
-            capture_output=True, text=True)
-        if r.returncode:
-            raise RuntimeError("hostsim_plant build failed:\n" + r.stderr[-3000:])
-        os.replace(tmp, so)
-    L = C.CDLL(so)
-    L.hostsim_plant.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int64, C.c_void_p,
-                                C.c_void_p, C.c_void_p, C.c_void_p]
-    _libs[key] = L
-    return L
+def lib_static(table, plain_only=False):
+    """the rows on `table` as a compile-time table (built-in arms, compiled plugins, general-inertia arms)"""
+    key, hdr = hostsim_build.table_header(_BUILD, table, "Tab_hostsim_plant")
+    return _build(key, ["-include", hdr, "-DHOSTSIM_PLANT_TAB=abrk::Tab_hostsim_plant"], plain_only)
 
 
-def lib_static(table):
-    """the plant row on `table` as a compile-time table (built-in arms, compiled plugins, general-inertia arms)"""
-    src = _abi.render_tab_struct(table, "Tab_hostsim_plant")
-    key = hashlib.sha256(src.encode()).hexdigest()[:16]
-    os.makedirs(_BUILD, exist_ok=True)
-    hdr = os.path.join(_BUILD, f"tab_{key}.h")
-    if not os.path.exists(hdr):
-        tmp = f"{hdr}.{os.getpid()}.tmp"
-        with open(tmp, "w") as fh:
-            fh.write("#pragma once\nnamespace abrk {\n" + src + "\n}  // namespace abrk\n")
-        os.replace(tmp, hdr)
-    return _build(key, ["-include", hdr, "-DHOSTSIM_PLANT_TAB=abrk::Tab_hostsim_plant"])
+def lib_runtime(n, plain_only=False):
+    return _build(f"rt{n}", [f"-DHOSTSIM_PLANT_RT_N={n}"], plain_only)
 
 
-def lib_runtime(n):
-    return _build(f"rt{n}", [f"-DHOSTSIM_PLANT_RT_N={n}"])
-
-
-def _run(table, runtime, mode, dt, substeps, gravity, q, dq, u, dtype):
+def _run(table, runtime, plain, plain_only, mode, dt, substeps, gravity, q, dq, u, effects, tau_ext, wrench, dtype):
     dt_ = np.dtype(dtype)
     q = np.array(q, dtype=dt_, order="C")
     dq = np.array(dq, dtype=dt_, order="C")
     u = np.ascontiguousarray(u, dtype=dt_)
+    ext = None if tau_ext is None else np.ascontiguousarray(tau_ext, dtype=dt_)
+    w = None if wrench is None else np.ascontiguousarray(wrench, dtype=dt_)
+    assert ext is None or ext.shape == q.shape
+    assert w is None or w.shape == (q.shape[0], 6)
+    assert not plain_only or (effects is None and ext is None and w is None)
     ddq = np.full(q.shape, np.nan, dt_)
     if runtime:
-        L, desc = lib_runtime(int(table["n_joints"])), _abi.desc_from_table(table)
+        L, desc = lib_runtime(int(table["n_joints"]), plain_only), _abi.desc_from_table(table)
         dp = C.cast(C.byref(desc), C.c_void_p)
     else:
-        L, dp = lib_static(table), None
+        L, dp = lib_static(table, plain_only), None
     assert L.hostsim_plant_n() == q.shape[1]
-    rc = L.hostsim_plant(dp, 0 if dt_ == np.float64 else 1, mode, float(dt), int(substeps), int(bool(gravity)),
-                         q.shape[0], q.ctypes.data, dq.ctypes.data, u.ctypes.data, ddq.ctypes.data)
+    rc = L.hostsim_plant(dp, 0 if dt_ == np.float64 else 1, int(plain or plain_only), mode, float(dt), int(substeps),
+                         int(bool(gravity)), None if effects is None else C.byref(effects), q.shape[0], q.ctypes.data,
+                         dq.ctypes.data, u.ctypes.data, None if ext is None else ext.ctypes.data,
+                         None if w is None else w.ctypes.data, ddq.ctypes.data)
     assert rc in (0, 1), rc
     return q, dq, ddq, rc == 1
 
 
-def forward_dynamics(table, q, dq, u, dtype=np.float64, runtime=False, gravity=True):
-    """-> ddq [B, n]"""
-    return _run(table, runtime, 0, 1.0, 1, gravity, q, dq, u, dtype)[2]
+def forward_dynamics(table, q, dq, u, effects=None, tau_ext=None, wrench=None, dtype=np.float64, runtime=False,
+                     gravity=True, plain=False, plain_only=False):
+    """-> ddq [B, n].  plain: the plain row program of the side-by-side build (effects, tau_ext and wrench ignored);
+    plain_only: the plain row program of the build that holds nothing else"""
+    return _run(table, runtime, plain, plain_only, 0, 1.0, 1, gravity, q, dq, u, effects, tau_ext, wrench, dtype)[2]
 
 
-def is_singular(table, q, dq, u, dtype=np.float64, runtime=False):
+def is_singular(table, q, dq, u, dtype=np.float64, runtime=False, plain=False, plain_only=False):
     """did a row's M meet a Cholesky pivot <= 0 (what the kernels report as ABRK_ESINGULAR)?"""
-    return _run(table, runtime, 0, 1.0, 1, True, q, dq, u, dtype)[3]
+    return _run(table, runtime, plain, plain_only, 0, 1.0, 1, True, q, dq, u, None, None, None, dtype)[3]
 
 
-def plant_step(table, dt, substeps, q, dq, u, dtype=np.float64, runtime=False, gravity=True):
+def plant_step(table, dt, substeps, q, dq, u, effects=None, tau_ext=None, wrench=None, dtype=np.float64,
+               runtime=False, gravity=True, plain=False, plain_only=False):
     """-> (q, dq) after one step of dt (copies; the inputs are left alone)"""
-    return _run(table, runtime, 1, dt, substeps, gravity, q, dq, u, dtype)[:2]
+    return _run(table, runtime, plain, plain_only, 1, dt, substeps, gravity, q, dq, u, effects, tau_ext, wrench,
+                dtype)[:2]

@@ -2,58 +2,33 @@
 built for the host, one small library per arm table (compile-time tables) or per joint count (runtime tables).  Never
 imported by the product."""
 import ctypes as C
-import hashlib
 import os
-import subprocess
 
 import numpy as np
 
 from abr_control_amd import _abi
+from tests import hostsim_build
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "..", "..", "abr_control_amd", "csrc")
 _BUILD = os.path.join(_HERE, "build")
+_DEPS = hostsim_build.csrc("abrk_device.h", "abrk_ctrl.h", "abrk_rows.h", "abrk_trace.h", "abrk_rt.h",
+                           "abrk_arms_builtin.h", "abrk_sincos_table.h")
 _libs = {}
 
 
-def _sources():
-    return [os.path.join(_HERE, "hostsim_trace.cpp")] + [
-        os.path.join(_CSRC, f) for f in ("abrk_device.h", "abrk_ctrl.h", "abrk_rows.h", "abrk_trace.h", "abrk_rt.h",
-                                         "abrk_arms_builtin.h", "abrk_sincos_table.h")]
-
-
-def _build(key, flags):
-    if key in _libs:
-        return _libs[key]
-    os.makedirs(_BUILD, exist_ok=True)
-    so = os.path.join(_BUILD, f"libhostsim_trace_{key}.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in _sources()):
-        tmp = f"{so}.{os.getpid()}.tmp"
-        r = subprocess.run(
-            ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O1", "-std=c++17", "-fPIC", "-shared",
-             "-fno-signed-zeros", "-ffinite-math-only", "--cuda-host-only", *flags, "-o", tmp, _sources()[0]],
-            capture_output=True, text=True)
-        if r.returncode:
-            raise RuntimeError("hostsim_trace build failed:\n" + r.stderr[-3000:])
-        os.replace(tmp, so)
-    L = C.CDLL(so)
-    L.hostsim_trace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_uint,
-                                C.c_double, C.c_int64] + [C.c_void_p] * 8
-    _libs[key] = L
-    return L
+def _build(key, defs):
+    if key not in _libs:
+        L = C.CDLL(hostsim_build.build(os.path.join(_HERE, "hostsim_trace.cpp"),
+                                       os.path.join(_BUILD, f"libhostsim_trace_{key}.so"), _DEPS, defs))
+        L.hostsim_trace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_uint,
+                                    C.c_double, C.c_int64] + [C.c_void_p] * 8
+        _libs[key] = L
+    return _libs[key]
 
 
 def lib_static(table):
     """the row on `table` as a compile-time table (built-in arms, compiled plugins)"""
-    src = _abi.render_tab_struct(table, "Tab_hostsim_trace")
-    key = hashlib.sha256(src.encode()).hexdigest()[:16]
-    os.makedirs(_BUILD, exist_ok=True)
-    hdr = os.path.join(_BUILD, f"tab_{key}.h")
-    if not os.path.exists(hdr):
-        tmp = f"{hdr}.{os.getpid()}.tmp"
-        with open(tmp, "w") as fh:
-            fh.write("#pragma once\nnamespace abrk {\n" + src + "\n}  // namespace abrk\n")
-        os.replace(tmp, hdr)
+    key, hdr = hostsim_build.table_header(_BUILD, table, "Tab_hostsim_trace")
     return _build(key, ["-include", hdr, "-DHOSTSIM_TRACE_TAB=abrk::Tab_hostsim_trace"])
 
 

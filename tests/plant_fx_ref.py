@@ -1,5 +1,5 @@
 """Reference of the plant with non-ideal effects (include/abrk.h, abrk_plant_effects), restated in NumPy on the oracle's
-M, C, g and J("EE", q) (general-inertia arms: the host build of the dynamics row program, tests/test_plant_hostsim.py
+M, C, g and J("EE", q) (general-inertia arms: the host build of the dynamics row program, tests/plant_ref.py
 HostsimGiDyn; their kinematics are the oracle's).  Per substep of h = dt / substeps:
   1. tau = clamp(u, -tau_max, +tau_max)
   2. tau += tau_ext + J^T w - damping dq - coulomb dq / sqrt(dq^2 + vs^2)        (q, dq of the substep's start)
@@ -12,7 +12,7 @@ import numpy as np
 
 from abr_control_amd import _abi
 from oracle.oracle import Oracle
-from tests.plant_ref import TOL_F32, TOL_F64, OracleDyn, rel_err  # noqa: F401  (re-exported to the tests)
+from tests.plant_ref import TOL_F32, TOL_F64, HostsimGiDyn, OracleDyn, gi_table, rel_err  # noqa: F401  (re-exported to the tests)
 
 # the effects of the issue's cases, on every joint
 ALL_ON = dict(damping=0.5, coulomb=0.3, coulomb_vs=0.01, tau_max=12.0, q_min=-2.0, q_max=2.0, restitution=0.5)

@@ -1,9 +1,13 @@
 """Reference values of the plant tests: the oracle's M, C, g composed in NumPy (LU solve), and the plain loop of the
 reference's update (arms/twojoint/arm_sim.py:131-132).  Shared by the CPU and the GPU plant tests."""
+import json
+import os
+
 import numpy as np
 
 from oracle.oracle import Oracle
 
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 TOL_F64 = 1e-6   # the project's bars: max|d| / max|ref| per row
 TOL_F32 = 1e-4
 
@@ -20,6 +24,26 @@ class OracleDyn:
 
     def mcg(self, q, dq):
         return self.O.M(q), self.O.C(q, dq), self.O.g(q)
+
+
+class HostsimGiDyn:
+    """M, C, g of a general-inertia table: the host build of the dynamics row program, which tests/test_general_inertia.py
+    pins to the reference's fixtures (the oracle library knows diagonal inertias only)"""
+
+    def __init__(self, table):
+        self.table = table
+
+    def mcg(self, q, dq):
+        from tests import hostsim_gi
+
+        r = hostsim_gi.dynamics(self.table, q[None], dq[None], want=("M", "g", "C"))
+        return r["M"][0], r["C"][0], r["g"][0]
+
+
+def gi_table(name):
+    """the general-inertia arm table of tests/golden/inertia_<name>.json, as committed (not normalised)"""
+    with open(os.path.join(GOLDEN, f"inertia_{name}.json")) as fh:
+        return json.load(fh)
 
 
 class Ref:

@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 from abr_control_amd import _abi
-from tests.plant_fx_ref import ALL_ON, BAND, CAP, TOL_F32, TOL_F64, OracleDyn, RefFx, draw, effects_rounded, \
-    effects_struct, rel_err, rounded
+from tests.plant_fx_ref import ALL_ON, BAND, CAP, TOL_F32, TOL_F64, HostsimGiDyn, OracleDyn, RefFx, draw, \
+    effects_rounded, effects_struct, rel_err, rounded
 
 pytestmark = pytest.mark.gpu
 BATCHES = (1, 63, 64, 65, 130)
@@ -37,8 +37,6 @@ def _config(name):
         assert rc.plugin_path, "no synthetic4 plugin for the current headers - run build()"
         return rc, RefFx(OracleDyn(tab), tab)
     assert name.startswith("gi_")
-    from tests.test_plant_hostsim import HostsimGiDyn
-
     tab = compiled_inertia_arms.table(name[3:])
     ntab = _abi.normalize_table(tab)
     return arms.from_table(tab), RefFx(HostsimGiDyn(ntab), ntab)

@@ -1,5 +1,5 @@
 """The row program of the plant with non-ideal effects (abrk_ctrl.h plant_fx_row) built for the host
-(tests/hostsim_plant_fx) against the NumPy reference (tests/plant_fx_ref.py): each effect alone, then all together, ddq
+(tests/hostsim_plant) against the NumPy reference (tests/plant_fx_ref.py): each effect alone, then all together, ddq
 and one step of 1 ms at substeps 1 and 4; and its bits against the plain row program when nothing is switched on.
 130 rows of seed 41 per case; bars: 1e-6 (fp64) and 1e-4 (fp32) on max|d| / max|ref| per row, every row counted except
 those the float64 reference finds within the band of a joint limit (none for fp64, at most one for fp32)."""
@@ -7,10 +7,9 @@ import numpy as np
 import pytest
 
 from abr_control_amd import _abi
-from tests import hostsim_plant_fx as hs
-from tests.plant_fx_ref import ALL_ON, BAND, CAP, TOL_F32, TOL_F64, OracleDyn, RefFx, draw, effects_rounded, \
-    effects_struct, rel_err, rounded
-from tests.test_plant_hostsim import HostsimGiDyn, _gi
+from tests import hostsim_plant as hs
+from tests.plant_fx_ref import ALL_ON, BAND, CAP, TOL_F32, TOL_F64, HostsimGiDyn, OracleDyn, RefFx, draw, \
+    effects_rounded, effects_struct, gi_table, rel_err, rounded
 
 B = 130
 SEED = 41
@@ -30,7 +29,7 @@ VARIANTS = {
 def _case(name):
     """-> (table, runtime, reference)"""
     if name.startswith("gi_"):
-        tab = _abi.normalize_table(_gi(name[3:]))
+        tab = _abi.normalize_table(gi_table(name[3:]))
         return tab, False, RefFx(HostsimGiDyn(tab), tab)
     tab = _abi.load_table("ur5" if name == "ur5_rt" else name)
     return tab, name == "ur5_rt", RefFx(OracleDyn(tab), tab)
@@ -121,7 +120,5 @@ def test_plant_fx_hostsim_everything_off_is_the_plain_row_bitwise(name, dtype):
         assert np.array_equal(hs.forward_dynamics(tab, q, dq, u, S, ext, w, dtype=dtype, runtime=rt), plain_ddq)
         a = hs.plant_step(tab, 1e-3, 4, q, dq, u, S, ext, w, dtype=dtype, runtime=rt)
         assert np.array_equal(a[0], plain_step[0]) and np.array_equal(a[1], plain_step[1])
-    # and the side-by-side build's plain row is the one tests/hostsim_plant builds
-    from tests import hostsim_plant
-
-    assert np.array_equal(hostsim_plant.forward_dynamics(tab, q, dq, u, dtype=dtype, runtime=rt), plain_ddq)
+    # and the side-by-side build's plain row is the one of the build that holds no other
+    assert np.array_equal(hs.forward_dynamics(tab, q, dq, u, dtype=dtype, runtime=rt, plain_only=True), plain_ddq)

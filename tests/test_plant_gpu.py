@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from abr_control_amd import _abi
-from tests.plant_ref import TOL_F32, TOL_F64, OracleDyn, Ref, draw, rel_err
+from tests.plant_ref import TOL_F32, TOL_F64, HostsimGiDyn, OracleDyn, Ref, draw, rel_err
 
 pytestmark = pytest.mark.gpu
 BATCHES = (1, 63, 64, 65, 130)
@@ -34,8 +34,6 @@ def _config(name):
         assert rc.plugin_path, "no synthetic4 plugin for the current headers - run build()"
         return rc, Ref(OracleDyn(tab))
     assert name.startswith("gi_")
-    from tests.test_plant_hostsim import HostsimGiDyn
-
     tab = compiled_inertia_arms.table(name[3:])
     return arms.from_table(tab), Ref(HostsimGiDyn(_abi.normalize_table(tab)))
 

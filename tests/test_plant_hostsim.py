@@ -1,7 +1,7 @@
 """The plant row program (abrk_ctrl.h plant_row) built for the host (tests/hostsim_plant) against the oracle composed in
 NumPy: ddq = solve(M, u - C dq - g) per row and the plain loop of dq += ddq h, q += dq h.  32 rows per case, no row left
 out; bars: 1e-6 (fp64) and 1e-4 (fp32) on max|d| / max|ref| per row."""
-import json
+import functools
 import os
 
 import numpy as np
@@ -9,35 +9,19 @@ import pytest
 
 from abr_control_amd import _abi
 from tests import hostsim_plant
-from tests.plant_ref import TOL_F32, TOL_F64, OracleDyn, Ref, draw, rel_err
+from tests.plant_ref import GOLDEN, TOL_F32, TOL_F64, HostsimGiDyn, OracleDyn, Ref, draw, gi_table, rel_err
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 B = 32
-
-
-class HostsimGiDyn:
-    """M, C, g of a general-inertia table: the host build of the dynamics row program, which tests/test_general_inertia.py
-    pins to the reference's fixtures (the oracle library knows diagonal inertias only)"""
-
-    def __init__(self, table):
-        self.table = table
-
-    def mcg(self, q, dq):
-        from tests import hostsim_gi
-
-        r = hostsim_gi.dynamics(self.table, q[None], dq[None], want=("M", "g", "C"))
-        return r["M"][0], r["C"][0], r["g"][0]
-
-
-def _gi(name):
-    with open(os.path.join(GOLDEN, f"inertia_{name}.json")) as fh:
-        return json.load(fh)
+# the build that holds the plain row program alone
+forward_dynamics = functools.partial(hostsim_plant.forward_dynamics, plain_only=True)
+is_singular = functools.partial(hostsim_plant.is_singular, plain_only=True)
+plant_step = functools.partial(hostsim_plant.plant_step, plain_only=True)
 
 
 def _case(name):
     """-> (table, runtime, reference)"""
     if name.startswith("gi_"):
-        tab = _abi.normalize_table(_gi(name[3:]))
+        tab = _abi.normalize_table(gi_table(name[3:]))
         return tab, False, Ref(HostsimGiDyn(tab))
     if name == "ur5_rt":
         tab = _abi.load_table("ur5")
@@ -63,18 +47,18 @@ def test_plant_hostsim_ddq_and_one_step(name, dtype):
         # reference value is numpy's LinAlgError, and the row program raises the flag the kernels report as ESINGULAR
         with pytest.raises(np.linalg.LinAlgError):
             ref.ddq(q, dq, u)
-        assert hostsim_plant.is_singular(tab, q, dq, u, dtype=dtype)
+        assert is_singular(tab, q, dq, u, dtype=dtype)
         return
-    assert not hostsim_plant.is_singular(tab, q, dq, u, dtype=dtype, runtime=rt)
-    got = hostsim_plant.forward_dynamics(tab, q, dq, u, dtype=dtype, runtime=rt)
+    assert not is_singular(tab, q, dq, u, dtype=dtype, runtime=rt)
+    got = forward_dynamics(tab, q, dq, u, dtype=dtype, runtime=rt)
     e = rel_err(got, ref.ddq(q, dq, u))
     print(f"{name} {np.dtype(dtype).name} ddq {e:.2e}")
     assert e <= tol
-    e0 = rel_err(hostsim_plant.forward_dynamics(tab, q, dq, u, dtype=dtype, runtime=rt, gravity=False),
+    e0 = rel_err(forward_dynamics(tab, q, dq, u, dtype=dtype, runtime=rt, gravity=False),
                  ref.ddq(q, dq, u, gravity=False))
     assert e0 <= tol
     for sub in (1, 4):
-        qg, dqg = hostsim_plant.plant_step(tab, 1e-3, sub, q, dq, u, dtype=dtype, runtime=rt)
+        qg, dqg = plant_step(tab, 1e-3, sub, q, dq, u, dtype=dtype, runtime=rt)
         qr, dqr = ref.steps(q, dq, u, 1e-3, sub)
         eq, edq = rel_err(qg, qr), rel_err(dqg, dqr)
         print(f"{name} {np.dtype(dtype).name} substeps {sub}: q {eq:.2e} dq {edq:.2e}")
@@ -84,12 +68,12 @@ def test_plant_hostsim_ddq_and_one_step(name, dtype):
 def test_plant_hostsim_gi_ddq_against_the_fixture():
     """the general-inertia table whose fixture carries M, g AND C (synthetic4), at the fixture's own 12 states: the
     reference's SymPy output composed in NumPy.  Worst measured: 5.0e-15."""
-    tab = _abi.normalize_table(_gi("synthetic4"))
+    tab = _abi.normalize_table(gi_table("synthetic4"))
     z = np.load(os.path.join(GOLDEN, "inertia_synthetic4.npz"))
     q, dq = z["dyn_q"], z["dyn_dq"]
     u = draw(12, q.shape[0], q.shape[1])[2]
     ref = np.stack([np.linalg.solve(z["M"][b], u[b] - z["C"][b] @ dq[b] - z["g"][b]) for b in range(q.shape[0])])
-    e = rel_err(hostsim_plant.forward_dynamics(tab, q, dq, u), ref)
+    e = rel_err(forward_dynamics(tab, q, dq, u), ref)
     print(f"gi synthetic4 vs fixture {e:.2e}")
     assert e <= TOL_F64
 
@@ -101,7 +85,7 @@ def test_plant_hostsim_fifty_steps(name):
     q, dq, u = draw(13, B, int(tab["n_joints"]))
     qg, dqg = q, dq
     for _ in range(50):
-        qg, dqg = hostsim_plant.plant_step(tab, 1e-3, 1, qg, dqg, u)
+        qg, dqg = plant_step(tab, 1e-3, 1, qg, dqg, u)
     qr, dqr = ref.steps(q, dq, u, 1e-3, 1, 50)
     eq, edq = rel_err(qg, qr), rel_err(dqg, dqr)
     print(f"{name} 50 steps: q {eq:.2e} dq {edq:.2e}")
@@ -119,6 +103,6 @@ def test_plant_hostsim_inverse_dynamics_identity(name):
     for b in range(B):
         M, Cm, g = ref.dyn(q[b], dq[b])
         u[b] = M @ a[b] + Cm @ dq[b] + g
-    e = rel_err(hostsim_plant.forward_dynamics(tab, q, dq, u, runtime=rt), a)
+    e = rel_err(forward_dynamics(tab, q, dq, u, runtime=rt), a)
     print(f"{name} identity {e:.2e}")
     assert e <= TOL_F64
