@@ -6,12 +6,14 @@
 
 #include "abrk_osc6_plan.h"
 #include "abrk_rows.h"
+#include "abrk_select.h"
 #include "abrk_trace.h"
 
 namespace abrk {
 
 constexpr int kBlock = 64;  // rows are independent, no LDS sharing: one wavefront per workgroup
 static_assert(kBlock == kOsc6ChunkRows, "the six-row plan counts chunks of one first-pass wavefront");
+static_assert(kWantVelocityOutputs == (W_C | W_DJ), "abrk_select.h names the velocity-dependent outputs by their bits");
 constexpr int kMinWaves = 1;  // kernels without a register cap: whatever occupancy their register count allows
 // Measurement switches of the host-side launch logic (ABRK_NO_HANDOVER, ABRK_FINISH_SLOTS, ABRK_OBS_PLAIN, ...: listed in
 // INTEGRATION.md) are read only when ABRK_MEASUREMENT=1 is set: no stray environment variable changes which algorithm a
@@ -607,8 +609,6 @@ constexpr long kObstaclesMaxBlocks = 4096;
 // 33 KiB in fp64), the pair list and one round of contributions - 40 KiB, four wavefronts per CU.
 constexpr int kObsPairCap = 2048;  // pairs of a wavefront that are redistributed; a lane beyond works its own off
 template <class A, class T>
-constexpr bool obstacles_use_lds() { return A::kOrtho && A::N >= 3; }
-template <class A, class T>
 __global__ void __launch_bounds__(kBlock, kMinWaves)
 obstacles_lds_kernel(A arm, ObsP<T> P, long B, const T* __restrict__ qg, T* __restrict__ ug, int acc) {
   constexpr int N = A::N, RL = obs_rec_len<N>();
@@ -822,52 +822,25 @@ struct Launch {
     T** po = reinterpret_cast<T**>(&o);
     for (int i = 0; i < 10; i++) po[i] = static_cast<T*>(a.out[i]);
     A arm = arm_of(la);
-    if (a.want & (W_C | W_DJ))
-      hipLaunchKernelGGL((dyn_kernel<A, T, true>), grid_for(la.B), dim3(kBlock), 0, la.stream, arm, a.frame, a.m,
+    auto go = [&](auto with_dq) {
+      hipLaunchKernelGGL((dyn_kernel<A, T, with_dq()>), grid_for(la.B), dim3(kBlock), 0, la.stream, arm, a.frame, a.m,
                          T(a.off[0]), T(a.off[1]), T(a.off[2]), a.want, la.B, (const T*)a.q, (const T*)a.dq, o);
-    else
-      hipLaunchKernelGGL((dyn_kernel<A, T, false>), grid_for(la.B), dim3(kBlock), 0, la.stream, arm, a.frame, a.m,
-                         T(a.off[0]), T(a.off[1]), T(a.off[2]), a.want, la.B, (const T*)a.q, (const T*)a.dq, o);
+    };
+    if (dyn_with_dq(a.want)) go(std::true_type{});
+    else go(std::false_type{});
     return hipGetLastError();
   }
-  template <int KM, bool UC, int FEAT>
+  // one variant V (abrk_select.h OscV) of the law alone, in the form `a.form` asks for: its passes and grids
+  template <class V>
   static hipError_t osc_launch(const LaunchArgs& la, const OscArgs& a) {
-    // the first pass of the plain six-row law has an instantiation for "ref_frame is the end effector" (EEF: no frame
-    // capture in the forward kinematics; the same bits) - the reference benchmark's setting
-    // Built for orthogonal built-in / compiled chains (where it was measured, UR5 8 M rows -1.6 %); general chains keep the
-    // capture (their EEF first pass faulted on the four-joint test arm: profiles/round6/NOTES.md section 2).  EVERY
-    // pass of such a launch takes the EEF form (first pass, recompute pass, one-pass): the capture changes the basic-block
-    // structure of the forward kinematics, and with it which multiply the compiler fuses with which add in its
-    // `c a0 + s a1` shapes - a row's bits must not depend on the pass that evaluates it.
-    // (general-inertia arms keep the capture too: the EEF form was measured on plain chains only)
-    constexpr bool kEefBuilt = osc_ortho<A>() && km6_first_pass_plain(KM, UC, FEAT, osc_ortho<A>(), 1, A::kStatic);
-    const bool eef = kEefBuilt && static_cast<const OscP<T>*>(a.P)->ref_frame == 2 * A::N + 1;
-    auto launch = [&](auto pass, auto nots_, auto eef_, dim3 grid, int mode) {
-      hipLaunchKernelGGL((osc_kernel<A, T, KM, UC, FEAT, pass(), nots_(), eef_()>), grid, dim3(kBlock), 0, la.stream,
+    constexpr int KM = V::km, FEAT = V::feat;
+    constexpr bool UC = V::use_c;
+    auto go = [&](auto pass, dim3 grid, int mode) {
+      hipLaunchKernelGGL((osc_kernel<A, T, KM, UC, FEAT, pass(), V::nots, V::eef>), grid, dim3(kBlock), 0, la.stream,
                          arm_of(la), *static_cast<const OscP<T>*>(a.P), la.B, (const T*)a.q, (const T*)a.dq,
                          (const T*)a.target, (const T*)a.tv, (T*)a.ierr, (const T*)a.une, (T*)a.u,
-                         nots_() ? (T*)nullptr : (T*)a.ts, mode, a.wl, (T*)a.rec);
+                         V::nots ? (T*)nullptr : (T*)a.ts, mode, a.wl, (T*)a.rec);
     };
-    using std::false_type;
-    using std::true_type;
-    auto go = [&](auto pass, dim3 grid, int mode) {
-      if constexpr (kEefBuilt && FEAT == 0) {
-        if (eef) return launch(pass, false_type{}, true_type{}, grid, mode);
-      }
-      launch(pass, false_type{}, false_type{}, grid, mode);
-    };
-    // the plain six-row law when no training signal is asked for (NOTS: gravity joins the velocity term before the
-    // factorisations).  EVERY form of the law then runs that arithmetic - first pass, recompute pass, one-pass - so
-    // that a row's bits do not depend on the batch it arrives in.
-    auto go_nots = [&](auto pass, dim3 grid, int mode) {
-      if constexpr (KM == 6 && FEAT == 0) {
-        if constexpr (kEefBuilt) {
-          if (eef) return launch(pass, true_type{}, true_type{}, grid, mode);
-        }
-        launch(pass, true_type{}, false_type{}, grid, mode);
-      }
-    };
-    const bool nots = KM == 6 && FEAT == 0 && !a.ts;
     if constexpr (KM == 6) {
       if (a.form != Osc6Form::OnePass) {
         const bool worklist = osc6_uses_worklist(a.form);
@@ -881,30 +854,24 @@ struct Launch {
         // (the persistent-grid form of the first pass: a multiple of kWlLists)
         constexpr bool plain = km6_first_pass_plain(KM, UC, FEAT, osc_ortho<A>(), 1, A::kStatic);
         if (!plain && g1.x > kKm6GridCap) g1.x = kKm6GridCap;
-        if (nots) go_nots(ic<1>{}, g1, 1);
-        else go(ic<1>{}, g1, 1);
-        if (worklist) {  // a multiple of kWlLists: 8 blocks stride each sub-list
-          if (nots) go_nots(ic<0>{}, dim3(8 * kWlLists), 2);
-          else go(ic<0>{}, dim3(8 * kWlLists), 2);
-        }
+        go(ic<1>{}, g1, 1);
+        if (worklist) go(ic<0>{}, dim3(8 * kWlLists), 2);  // a multiple of kWlLists: 8 blocks stride each sub-list
         return hipSuccess;
       }
     }
-    if (nots) go_nots(ic<0>{}, grid_for(la.B), 0);
-    else go(ic<0>{}, grid_for(la.B), 0);
+    go(ic<0>{}, grid_for(la.B), 0);
     return hipSuccess;
   }
-  template <int KM, bool UC>
-  static hipError_t osc_launch_feat(const LaunchArgs& la, const OscArgs& a) {
-    // which optional inputs are present?  0: none, 1: fused null controllers only, 2: anything else
-    const bool other = a.tv || a.ierr || a.une;
-    const bool nulls = static_cast<const OscP<T>*>(a.P)->n_null > 0;
-    if (other) return osc_launch<KM, UC, 2>(la, a);
-    if (nulls) return osc_launch<KM, UC, 1>(la, a);
-    return osc_launch<KM, UC, 0>(la, a);
+  // the kernel <KM, UC, FEAT> whatever the call's optional inputs; its NOTS / EEF twin as the call asks
+  // (tools/microbench/kernel_ab.hip)
+  template <int KM, bool UC, int FEAT>
+  static hipError_t osc_launch_fixed(const LaunchArgs& la, const OscArgs& a) {
+    const OscVariant v{KM, UC, FEAT, osc_nots(KM, FEAT, a.ts != nullptr), false, false};
+    return with_osc_twin<A, KM, UC, FEAT>(v.nots, osc_eef<A>(v, static_cast<const OscP<T>*>(a.P)->ref_frame),
+                                          [&](auto vt) { return osc_launch<decltype(vt)>(la, a); });
   }
-  template <int KM, bool UC, int FEAT, bool VEL>
-  static void osc_full_launch(const LaunchArgs& la, const OscArgs& a) {
+  template <class V>
+  static hipError_t osc_full_launch(const LaunchArgs& la, const OscArgs& a) {
     DynOutP<T> o{};
     o.Tx = (T*)a.out[0];
     o.J = (T*)a.out[1];
@@ -912,40 +879,20 @@ struct Launch {
     o.g = (T*)a.out[3];
     o.C = (T*)a.out[4];
     o.dJ = (T*)a.out[5];
-    hipLaunchKernelGGL((osc_full_kernel<A, T, KM, UC, FEAT, VEL>), grid_for(la.B), dim3(kBlock), 0, la.stream, arm_of(la),
-                       *static_cast<const OscP<T>*>(a.P), la.B, (const T*)a.q, (const T*)a.dq, (const T*)a.target,
-                       (const T*)a.tv, (T*)a.ierr, (const T*)a.une, (T*)a.u, (T*)a.ts, a.want, o);
-  }
-  template <int KM, bool UC>
-  static void osc_full_feat(const LaunchArgs& la, const OscArgs& a) {
-    const bool plain = !(a.tv || a.ierr || a.une) && static_cast<const OscP<T>*>(a.P)->n_null == 0;
-    // C / dJ among the outputs: the variant whose dynamics pass assembles the Christoffel matrix (FEAT 2 only: the
-    // velocity-dependent outputs are the rarer request and one instantiation per (KM, use_C) keeps the build in bounds)
-    if (a.want & (W_C | W_DJ)) osc_full_launch<KM, UC, 2, true>(la, a);
-    else if (plain) osc_full_launch<KM, UC, 0, false>(la, a);
-    else osc_full_launch<KM, UC, 2, false>(la, a);
-  }
-  static hipError_t osc_full(const LaunchArgs& la, const OscArgs& a) {
-    // the two-row kernel of the planar examples is not duplicated: x,y control of a small arm takes the six-row form
-    if (a.fast == 3) {
-      if (a.use_C) osc_full_feat<3, true>(la, a);
-      else osc_full_feat<3, false>(la, a);
-    } else {
-      if (a.use_C) osc_full_feat<6, true>(la, a);
-      else osc_full_feat<6, false>(la, a);
-    }
-    return hipGetLastError();
+    hipLaunchKernelGGL((osc_full_kernel<A, T, V::km, V::use_c, V::feat, V::vel>), grid_for(la.B), dim3(kBlock), 0,
+                       la.stream, arm_of(la), *static_cast<const OscP<T>*>(a.P), la.B, (const T*)a.q, (const T*)a.dq,
+                       (const T*)a.target, (const T*)a.tv, (T*)a.ierr, (const T*)a.une, (T*)a.u, (T*)a.ts, a.want, o);
+    return hipSuccess;
   }
   static hipError_t osc(const LaunchArgs& la, const OscArgs& a) {
-    if (a.want) return osc_full(la, a);
-    hipError_t e = hipSuccess;
-    if (a.fast == 3) {
-      e = a.use_C ? osc_launch_feat<3, true>(la, a) : osc_launch_feat<3, false>(la, a);
-    } else if (a.fast == 2 && A::N <= 3) {
-      if constexpr (A::N <= 3) e = a.use_C ? osc_launch_feat<2, true>(la, a) : osc_launch_feat<2, false>(la, a);
-    } else {
-      e = a.use_C ? osc_launch_feat<6, true>(la, a) : osc_launch_feat<6, false>(la, a);
-    }
+    const OscP<T>& P = *static_cast<const OscP<T>*>(a.P);
+    const OscVariant v = osc_variant(a.fast, A::N, a.use_C != 0, P.n_null, a.tv != nullptr, a.ierr != nullptr,
+                                     a.une != nullptr, a.ts != nullptr, a.want);
+    const hipError_t e = with_osc_variant<A>(v, osc_eef<A>(v, P.ref_frame), [&](auto vt) {
+      using V = decltype(vt);
+      if constexpr (V::full) return osc_full_launch<V>(la, a);
+      else return osc_launch<V>(la, a);
+    });
     return e != hipSuccess ? e : hipGetLastError();
   }
   static hipError_t sliding(const LaunchArgs& la, const SlidingArgs& a) {
@@ -983,98 +930,69 @@ struct Launch {
     hipLaunchKernelGGL((trace_kernel<A, T>), grid_for(la.B), dim3(kBlock), 0, la.stream, arm_of(la), P, la.B, io);
     return hipGetLastError();
   }
-};
-
-// ops for an arm policy available in both arithmetic types (AD = double flavour, AF = float)
-template <class AD, class AF>
-struct OpsFor {
-  static hipError_t dyn(int dt, const LaunchArgs& la, const DynArgs& a) {
-    return dt == 0 ? Launch<AD, double>::dyn(la, a) : Launch<AF, float>::dyn(la, a);
-  }
-  static hipError_t osc(int dt, const LaunchArgs& la, const OscArgs& a) {
-    return dt == 0 ? Launch<AD, double>::osc(la, a) : Launch<AF, float>::osc(la, a);
-  }
-  static hipError_t sliding(int dt, const LaunchArgs& la, const SlidingArgs& a) {
-    return dt == 0 ? Launch<AD, double>::sliding(la, a) : Launch<AF, float>::sliding(la, a);
-  }
-  static hipError_t joint(int dt, const LaunchArgs& la, const JointArgs& a) {
-    return dt == 0 ? Launch<AD, double>::joint(la, a) : Launch<AF, float>::joint(la, a);
-  }
-  template <class A, class T>
-  static hipError_t rollout_t(const LaunchArgs& la, const RolloutArgs& a) {
+  static hipError_t rollout(const LaunchArgs& la, const RolloutArgs& a) {
     if constexpr (A::N == 2) {
-      A arm = Launch<A, T>::arm_of(la);
-      auto go = [&](auto uc, auto km) {
-        hipLaunchKernelGGL((rollout_kernel<A, T, uc(), km()>), grid_for(la.B), dim3(kBlock), 0, la.stream, arm,
+      with_rollout_variant(a.fast, a.use_C != 0, [&](auto uc, auto km) {
+        hipLaunchKernelGGL((rollout_kernel<A, T, uc(), km()>), grid_for(la.B), dim3(kBlock), 0, la.stream, arm_of(la),
                            *static_cast<const OscP<T>*>(a.P), *static_cast<const TwoLinkP<T>*>(a.K), la.B, a.n_steps,
                            a.every, (T*)a.q, (T*)a.dq, (const T*)a.target, (T*)a.ierr, (T*)a.qt, (T*)a.dqt, (T*)a.ut);
-      };
-      using std::integral_constant;
-      if (a.fast == 2) {
-        if (a.use_C) go(integral_constant<bool, true>{}, integral_constant<int, 2>{});
-        else go(integral_constant<bool, false>{}, integral_constant<int, 2>{});
-      } else {
-        if (a.use_C) go(integral_constant<bool, true>{}, integral_constant<int, 6>{});
-        else go(integral_constant<bool, false>{}, integral_constant<int, 6>{});
-      }
+      });
       return hipGetLastError();
     } else {
       return hipErrorInvalidValue;
     }
   }
-  static hipError_t rollout(int dt, const LaunchArgs& la, const RolloutArgs& a) {
-    return dt == 0 ? rollout_t<AD, double>(la, a) : rollout_t<AF, float>(la, a);
-  }
-  template <class A, class T>
-  static hipError_t ik_t(const LaunchArgs& la, const IkArgs& a) {
-    hipLaunchKernelGGL((ik_kernel<A, T>), grid_for(la.B), dim3(kBlock), 0, la.stream, Launch<A, T>::arm_of(la),
+  static hipError_t ik(const LaunchArgs& la, const IkArgs& a) {
+    hipLaunchKernelGGL((ik_kernel<A, T>), grid_for(la.B), dim3(kBlock), 0, la.stream, arm_of(la),
                        *static_cast<const IkP<T>*>(a.P), la.B, (const T*)a.q, (const T*)a.target, (T*)a.pp, (T*)a.vp);
     return hipGetLastError();
   }
-  static hipError_t ik(int dt, const LaunchArgs& la, const IkArgs& a) {
-    return dt == 0 ? ik_t<AD, double>(la, a) : ik_t<AF, float>(la, a);
-  }
-  template <class A, class T>
-  static hipError_t floating_t(const LaunchArgs& la, const FloatingArgs& a) {
-    hipLaunchKernelGGL((floating_kernel<A, T>), grid_for(la.B), dim3(kBlock), 0, la.stream, Launch<A, T>::arm_of(la),
-                       a.dynamic, a.task_space, la.B, (const T*)a.q, (const T*)a.dq, (T*)a.u, a.acc);
+  static hipError_t floating(const LaunchArgs& la, const FloatingArgs& a) {
+    hipLaunchKernelGGL((floating_kernel<A, T>), grid_for(la.B), dim3(kBlock), 0, la.stream, arm_of(la), a.dynamic,
+                       a.task_space, la.B, (const T*)a.q, (const T*)a.dq, (T*)a.u, a.acc);
     return hipGetLastError();
   }
-  static hipError_t floating(int dt, const LaunchArgs& la, const FloatingArgs& a) {
-    return dt == 0 ? floating_t<AD, double>(la, a) : floating_t<AF, float>(la, a);
-  }
-  template <class A, class T>
-  static hipError_t obstacles_t(const LaunchArgs& la, const ObstaclesArgs& a) {
+  static hipError_t obstacles(const LaunchArgs& la, const ObstaclesArgs& a) {
     const long blocks = (la.B + kBlock - 1) / kBlock;
     const dim3 grid((unsigned)(blocks < kObstaclesMaxBlocks ? blocks : kObstaclesMaxBlocks));
     const ObsP<T>& P = *static_cast<const ObsP<T>*>(a.P);
-    if constexpr (obstacles_use_lds<A, T>()) {
+    if constexpr (obstacles_split_built<A>()) {
       static const bool off = measurement_env("ABRK_OBS_PLAIN") != nullptr;  // measurement switch: the one-pass kernel
-      if (!off && P.n * (A::N - 2) <= 64) {
-        hipLaunchKernelGGL((obstacles_lds_kernel<A, T>), grid, dim3(kBlock), 0, la.stream, Launch<A, T>::arm_of(la), P, la.B,
+      if (!off && obstacles_split<A>(P.n)) {
+        hipLaunchKernelGGL((obstacles_lds_kernel<A, T>), grid, dim3(kBlock), 0, la.stream, arm_of(la), P, la.B,
                            (const T*)a.q, (T*)a.u, a.acc);
         return hipGetLastError();
       }
     }
-    hipLaunchKernelGGL((obstacles_kernel<A, T>), grid, dim3(kBlock), 0, la.stream, Launch<A, T>::arm_of(la), P, la.B,
-                       (const T*)a.q, (T*)a.u, a.acc);
+    hipLaunchKernelGGL((obstacles_kernel<A, T>), grid, dim3(kBlock), 0, la.stream, arm_of(la), P, la.B, (const T*)a.q,
+                       (T*)a.u, a.acc);
     return hipGetLastError();
   }
-  static hipError_t obstacles(int dt, const LaunchArgs& la, const ObstaclesArgs& a) {
-    return dt == 0 ? obstacles_t<AD, double>(la, a) : obstacles_t<AF, float>(la, a);
-  }
-  static hipError_t plant(int dt, const LaunchArgs& la, const PlantArgs& a) {
-    return dt == 0 ? Launch<AD, double>::plant(la, a) : Launch<AF, float>::plant(la, a);
-  }
-  static hipError_t trace(int dt, const LaunchArgs& la, const TraceArgs& a) {
-    return dt == 0 ? Launch<AD, double>::trace(la, a) : Launch<AF, float>::trace(la, a);
-  }
-  static hipError_t plant_fx(int dt, const LaunchArgs& la, const PlantFxArgs& a) {
-    return dt == 0 ? Launch<AD, double>::plant_fx(la, a) : Launch<AF, float>::plant_fx(la, a);
+};
+
+// ops for an arm policy available in both arithmetic types (AD = double flavour, AF = float)
+template <class AD, class AF>
+struct OpsFor {
+  using LD = Launch<AD, double>;
+  using LF = Launch<AF, float>;
+  // one entry of the table: the launcher of the arithmetic type the call names
+  template <auto D, auto F, class Args>
+  static hipError_t by_dtype(int dt, const LaunchArgs& la, const Args& a) {
+    return dt == 0 ? D(la, a) : F(la, a);
   }
   static const ArmOps* ops() {
-    static const ArmOps o = {AD::N, &dyn, &osc, &sliding, &joint, AD::N == 2 ? &rollout : nullptr, &ik,
-                             &floating, &obstacles, &plant, &trace, &plant_fx};
+    static const ArmOps o = {AD::N,
+                             &by_dtype<&LD::dyn, &LF::dyn>,
+                             &by_dtype<&LD::osc, &LF::osc>,
+                             &by_dtype<&LD::sliding, &LF::sliding>,
+                             &by_dtype<&LD::joint, &LF::joint>,
+                             AD::N == 2 ? &by_dtype<&LD::rollout, &LF::rollout, RolloutArgs> : nullptr,  // two-joint arms only
+                             &by_dtype<&LD::ik, &LF::ik>,
+                             &by_dtype<&LD::floating, &LF::floating>,
+                             &by_dtype<&LD::obstacles, &LF::obstacles>,
+                             &by_dtype<&LD::plant, &LF::plant>,
+                             &by_dtype<&LD::trace, &LF::trace>,
+                             &by_dtype<&LD::plant_fx, &LF::plant_fx>};
     return &o;
   }
 };

@@ -10,14 +10,8 @@ static hipError_t law_launch(const LaunchArgs& la, const LawArgs& a) {
   return hipGetLastError();
 }
 hipError_t launch_osc_law(int n, int dtype, const LaunchArgs& la, const LawArgs& a) {
-#define ABRK_CASE(NN) \
-  case NN:            \
-    return dtype == 0 ? law_launch<NN, double>(la, a) : law_launch<NN, float>(la, a);
-  switch (n) {
-    ABRK_CASE(1) ABRK_CASE(2) ABRK_CASE(3) ABRK_CASE(4) ABRK_CASE(5) ABRK_CASE(6) ABRK_CASE(7)
-  }
-#undef ABRK_CASE
-  return hipErrorInvalidValue;
+  return for_joints_and_dtype(
+      n, dtype, [&](auto nn, auto t) { return law_launch<nn(), decltype(t)>(la, a); }, hipErrorInvalidValue);
 }
 // ---- finish kernels of the six-row law's hand-over forms (abrk_finish.h), launched as the plan says
 template <int N, class T>
@@ -59,14 +53,8 @@ hipError_t launch_osc6_finish(int n, int dtype, const LaunchArgs& la, const Fini
       ok = false;
   }
   if (!ok) return hipErrorInvalidValue;
-#define ABRK_CASE(NN) \
-  case NN:            \
-    return dtype == 0 ? finish_launch<NN, double>(la, a) : finish_launch<NN, float>(la, a);
-  switch (n) {
-    ABRK_CASE(1) ABRK_CASE(2) ABRK_CASE(3) ABRK_CASE(4) ABRK_CASE(5) ABRK_CASE(6) ABRK_CASE(7)
-  }
-#undef ABRK_CASE
-  return hipErrorInvalidValue;
+  return for_joints_and_dtype(
+      n, dtype, [&](auto nn, auto t) { return finish_launch<nn(), decltype(t)>(la, a); }, hipErrorInvalidValue);
 }
 template <int N, class T>
 static hipError_t limits_launch(const LaunchArgs& la, const void* P, const void* q, void* u, int acc) {
@@ -75,14 +63,9 @@ static hipError_t limits_launch(const LaunchArgs& la, const void* P, const void*
   return hipGetLastError();
 }
 hipError_t launch_limits(int n, int dtype, const LaunchArgs& la, const void* P, const void* q, void* u, int acc) {
-#define ABRK_CASE(NN) \
-  case NN:            \
-    return dtype == 0 ? limits_launch<NN, double>(la, P, q, u, acc) : limits_launch<NN, float>(la, P, q, u, acc);
-  switch (n) {
-    ABRK_CASE(1) ABRK_CASE(2) ABRK_CASE(3) ABRK_CASE(4) ABRK_CASE(5) ABRK_CASE(6) ABRK_CASE(7)
-  }
-#undef ABRK_CASE
-  return hipErrorInvalidValue;
+  return for_joints_and_dtype(
+      n, dtype, [&](auto nn, auto t) { return limits_launch<nn(), decltype(t)>(la, P, q, u, acc); },
+      hipErrorInvalidValue);
 }
 template <int N, class T>
 static hipError_t mx_launch(const LaunchArgs& la, int k, double thr, const void* M, const void* J, void* Mx, void* Minv) {
@@ -92,49 +75,40 @@ static hipError_t mx_launch(const LaunchArgs& la, int k, double thr, const void*
 }
 hipError_t launch_osc_mx(int n, int dtype, const LaunchArgs& la, int k, double thr, const void* M, const void* J,
                          void* Mx, void* Minv) {
-#define ABRK_CASE(NN) \
-  case NN:            \
-    return dtype == 0 ? mx_launch<NN, double>(la, k, thr, M, J, Mx, Minv) : mx_launch<NN, float>(la, k, thr, M, J, Mx, Minv);
-  switch (n) {
-    ABRK_CASE(1) ABRK_CASE(2) ABRK_CASE(3) ABRK_CASE(4) ABRK_CASE(5) ABRK_CASE(6) ABRK_CASE(7)
-  }
-#undef ABRK_CASE
-  return hipErrorInvalidValue;
+  return for_joints_and_dtype(
+      n, dtype, [&](auto nn, auto t) { return mx_launch<nn(), decltype(t)>(la, k, thr, M, J, Mx, Minv); },
+      hipErrorInvalidValue);
 }
 hipError_t launch_velocity_limiting(int dtype, const LaunchArgs& la, const double (&g)[5], const void* in, void* out) {
-  if (dtype == 0)
-    hipLaunchKernelGGL((velocity_limiting_kernel<double>), grid_for(la.B), dim3(kBlock), 0, la.stream, la.B, g[0], g[1],
-                       g[2], g[3], g[4], (const double*)in, (double*)out);
-  else
-    hipLaunchKernelGGL((velocity_limiting_kernel<float>), grid_for(la.B), dim3(kBlock), 0, la.stream, la.B, float(g[0]),
-                       float(g[1]), float(g[2]), float(g[3]), float(g[4]), (const float*)in, (float*)out);
+  for_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((velocity_limiting_kernel<T>), grid_for(la.B), dim3(kBlock), 0, la.stream, la.B, T(g[0]), T(g[1]),
+                       T(g[2]), T(g[3]), T(g[4]), (const T*)in, (T*)out);
+  });
   return hipGetLastError();
 }
 hipError_t launch_orientation_forces(int dtype, const LaunchArgs& la, int alg, const void* R, const void* abg, void* out) {
-  if (dtype == 0)
-    hipLaunchKernelGGL((orientation_forces_kernel<double>), grid_for(la.B), dim3(kBlock), 0, la.stream, la.B, alg,
-                       (const double*)R, (const double*)abg, (double*)out);
-  else
-    hipLaunchKernelGGL((orientation_forces_kernel<float>), grid_for(la.B), dim3(kBlock), 0, la.stream, la.B, alg,
-                       (const float*)R, (const float*)abg, (float*)out);
+  for_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((orientation_forces_kernel<T>), grid_for(la.B), dim3(kBlock), 0, la.stream, la.B, alg,
+                       (const T*)R, (const T*)abg, (T*)out);
+  });
   return hipGetLastError();
 }
 hipError_t launch_transformations(int dtype, const LaunchArgs& la, int op, const void* a, const void* b, void* out) {
-  if (dtype == 0)
-    hipLaunchKernelGGL((transformations_kernel<double>), grid_for(la.B), dim3(kBlock), 0, la.stream, la.B, op,
-                       (const double*)a, (const double*)b, (double*)out);
-  else
-    hipLaunchKernelGGL((transformations_kernel<float>), grid_for(la.B), dim3(kBlock), 0, la.stream, la.B, op,
-                       (const float*)a, (const float*)b, (float*)out);
+  for_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((transformations_kernel<T>), grid_for(la.B), dim3(kBlock), 0, la.stream, la.B, op, (const T*)a,
+                       (const T*)b, (T*)out);
+  });
   return hipGetLastError();
 }
 hipError_t launch_twolink_step(int dtype, const LaunchArgs& la, const void* K, void* q, void* dq, const void* u) {
-  if (dtype == 0)
-    hipLaunchKernelGGL((twolink_step_kernel<double>), grid_for(la.B), dim3(kBlock), 0, la.stream,
-                       *static_cast<const TwoLinkP<double>*>(K), la.B, (double*)q, (double*)dq, (const double*)u);
-  else
-    hipLaunchKernelGGL((twolink_step_kernel<float>), grid_for(la.B), dim3(kBlock), 0, la.stream,
-                       *static_cast<const TwoLinkP<float>*>(K), la.B, (float*)q, (float*)dq, (const float*)u);
+  for_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((twolink_step_kernel<T>), grid_for(la.B), dim3(kBlock), 0, la.stream,
+                       *static_cast<const TwoLinkP<T>*>(K), la.B, (T*)q, (T*)dq, (const T*)u);
+  });
   return hipGetLastError();
 }
 }  // namespace abrk

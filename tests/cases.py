@@ -79,16 +79,20 @@ _jt("jaco2", "damping", make_damping(10), False, no_target=True)
 def takes_plain_six_row_law(case_id):
     """True where the case runs the six-row kernels with no optional input (`osc_kernel<.., 6, .., FEAT = 0, ..>`: not the
     x,y,z / x,y fast paths of abrk_params.h osc_fast_rows, no target velocity, no integral state, no fused secondary
-    controller) - the law that has a `NOTS = true` twin for callers who ask for no training signal"""
+    controller) - the law that has a `NOTS = true` twin for callers who ask for no training signal.  The launcher's own
+    rule answers (csrc/abrk_select.h `osc_variant`, through the hostsim test aid)"""
+    from tests import hostsim
+
     case = CASES[case_id]
-    if case["kind"] != "osc" or case["tv"] or case["steps"] > 1:
+    if case["kind"] != "osc":
         return False
     n = _abi.load_table(case["arm"])["n_joints"]
     p = case["params"](n)
     dof = [int(bool(v)) for v in p.ctrlr_dof]
     ee = p.ref_frame == 2 * n + 1
-    fast = ee and (dof == XYZ or (dof == XY and n <= 3))
-    return not fast and p.n_null == 0 and p.ki == 0
+    fast = 0 if not ee else 3 if dof == XYZ else 2 if dof == XY and n <= 3 else 0
+    v = hostsim.osc_variant(fast, n, use_C=p.use_C, n_null=p.n_null, tv=case["tv"], ki=p.ki, ie=case["steps"] > 1)
+    return v["km"] == 6 and v["feat"] == 0
 
 
 def run_case(backend, case, g, dtype=np.float64, rows=None):

@@ -28,7 +28,7 @@ def _so(part):
 
 def build(force=False):
     deps = hostsim_build.csrc("abrk_device.h", "abrk_ctrl.h", "abrk_rows.h", "abrk_params.h", "abrk_rt.h",
-                              "abrk_arms_builtin.h", "abrk_sincos_table.h", "abrk_osc6_plan.h") + [hostsim_build.ABRK_H]
+                              "abrk_arms_builtin.h", "abrk_sincos_table.h", "abrk_osc6_plan.h", "abrk_select.h") + [hostsim_build.ABRK_H]
     hostsim_build.build_many(os.path.join(_HERE, "hostsim.cpp"), deps, {_so(p): d for p, d in PARTS.items()}, force)
     return [_so(p) for p in PARTS]
 
@@ -240,6 +240,19 @@ def osc6_plan(B, **switches):
     rc = _lib_for(law=True).hostsim_osc6_plan(C.c_int64(int(B)), C.c_uint(given), sw, out)
     assert rc == 0, rc
     return OSC6_FORMS[out[0]], out[1], out[2], out[3]
+
+
+def osc_variant(fast, n, use_C=False, n_null=0, tv=False, ki=0.0, ie=False, une=False, ts=True, want=0):
+    """the kernel variant an OSC call takes (csrc/abrk_select.h `osc_variant`): `fast` from osc_fast_rows, `n` joints,
+    which optional arrays the call presents (`ie` counts where ki != 0), whether a training signal is asked for and the
+    W_* bits of the fused outputs -> dict(km, use_c, feat, nots, full, vel)"""
+    out = (C.c_int * 6)()
+    rc = _lib_for(law=True).hostsim_osc_variant(int(fast), int(n), int(bool(use_C)), int(n_null), int(bool(tv)),
+                                                int(ki != 0), int(bool(ie)), int(bool(une)), int(bool(ts)),
+                                                C.c_uint(int(want)), out)
+    assert rc == 0, rc
+    km, use_c, feat, nots, full, vel = out
+    return dict(km=km, use_c=bool(use_c), feat=feat, nots=bool(nots), full=bool(full), vel=bool(vel))
 
 
 def sym6_eig(A, method):

@@ -14,6 +14,7 @@
 #include "../../abr_control_amd/csrc/abrk_params.h"
 #include "../../abr_control_amd/csrc/abrk_rows.h"
 #include "../../abr_control_amd/csrc/abrk_rt.h"
+#include "../../abr_control_amd/csrc/abrk_select.h"
 
 using namespace abrk;
 
@@ -42,54 +43,48 @@ int run_dyn(const A& arm, int n, int64_t B, const void* q, const void* dq, int f
   int m = frame_m(frame, n);
   T ox = T(off ? off[0] : 0), oy = T(off ? off[1] : 0), oz = T(off ? off[2] : 0);
   DirectStore<T> st;
-  for (long b = 0; b < B; b++) {
-    if (want & (W_C | W_DJ))
-      dyn_body<A, T, true>(b, true, st, arm, frame, m, ox, oy, oz, want, (long)B, (const T*)q, (const T*)dq, o);
-    else
-      dyn_body<A, T, false>(b, true, st, arm, frame, m, ox, oy, oz, want, (long)B, (const T*)q, (const T*)dq, o);
-  }
+  auto rows = [&](auto with_dq) {
+    for (long b = 0; b < B; b++)
+      dyn_body<A, T, with_dq()>(b, true, st, arm, frame, m, ox, oy, oz, want, (long)B, (const T*)q, (const T*)dq, o);
+  };
+  if (dyn_with_dq(want)) rows(std::true_type{});
+  else rows(std::false_type{});
   return 0;
+}
+// The variant of an OSC call, decided where the launcher decides it (abrk_select.h): the integral state is dropped for
+// ki == 0 as the host layer stages it.  with_variant: f(OscV) for the law alone (FULL = false) or the fused row program;
+// -1 for a variant of the other family (the aid has no EEF form: the same bits)
+template <class T>
+OscVariant variant_of(const abrk_osc_params& P, const OscP<T>& p, int n, const void* tv, void*& ie, const void* une,
+                      const void* ts, unsigned want) {
+  if (P.ki == 0) ie = nullptr;
+  return osc_variant(osc_fast_rows(P, n, une != nullptr), n, P.use_C != 0, p.n_null, tv != nullptr, ie != nullptr,
+                     une != nullptr, ts != nullptr, want);
+}
+template <class A, bool FULL, class F>
+int with_variant(const OscVariant& v, F&& f) {
+  return with_osc_variant<A>(v, [&](auto vt) {
+    using V = decltype(vt);
+    if constexpr (V::full == FULL && !V::eef) return f(vt);
+    else return -1;
+  });
 }
 template <class A, class T>
 int run_osc(const A& arm, int n, const abrk_osc_params* P, int64_t B, const void* q, const void* dq,
             const void* tg, const void* tv, void* ie, const void* une, void* u, void* ts) {
   OscP<T> p = make_oscp<T>(*P, n);
-  int fast = osc_fast_rows(*P, n, une != nullptr);
-  if (P->ki == 0) ie = nullptr;
-  const int feat = (tv || ie || une) ? 2 : (p.n_null > 0 ? 1 : 0);  // same dispatch rule as Launch::osc_launch_feat
-  for (long b = 0; b < B; b++) {
-#define CALL1(KM, UC, FT)                                                                                  \
-  osc_body<A, T, KM, UC, FT>(b, arm, p, (long)B, (const T*)q, (const T*)dq, (const T*)tg, (const T*)tv, (T*)ie, \
-                             (const T*)une, (T*)u, (T*)ts)
-#define CALL(KM, UC)                      \
-  do {                                    \
-    if (feat == 2) CALL1(KM, UC, 2);      \
-    else if (feat == 1) CALL1(KM, UC, 1); \
-    else CALL1(KM, UC, 0);                \
-  } while (0)
-    if (fast == 3) {
-      if (P->use_C) CALL(3, true); else CALL(3, false);
-    } else if (fast == 2) {
-      if constexpr (A::N <= 3) {
-        if (P->use_C) CALL(2, true); else CALL(2, false);
-      }
-    } else if (feat == 0 && !ts) {
-      // what the first pass of the plain six-row kernels runs when no training signal is asked for (NoTs: the gravity
-      // term folded into the velocity term ahead of the factorisations)
-      NoTs<RegScratch<T, A::N>> scr;
-      if (P->use_C)
-        osc_body<A, T, 6, true, 0>(b, arm, p, (long)B, (const T*)q, (const T*)dq, (const T*)tg, (const T*)tv, (T*)ie,
-                                   (const T*)une, (T*)u, (T*)ts, scr);
-      else
-        osc_body<A, T, 6, false, 0>(b, arm, p, (long)B, (const T*)q, (const T*)dq, (const T*)tg, (const T*)tv, (T*)ie,
-                                    (const T*)une, (T*)u, (T*)ts, scr);
-    } else {
-      if (P->use_C) CALL(6, true); else CALL(6, false);
+  const OscVariant v = variant_of(*P, p, n, tv, ie, une, ts, 0);
+  return with_variant<A, false>(v, [&](auto vt) {
+    using V = decltype(vt);
+    for (long b = 0; b < B; b++) {
+      // (NOTS: what every pass of the plain six-row kernels runs when no training signal is asked for - the gravity
+      //  term folded into the velocity term ahead of the factorisations)
+      std::conditional_t<V::nots, NoTs<RegScratch<T, A::N>>, RegScratch<T, A::N>> scr;
+      osc_body<A, T, V::km, V::use_c, V::feat>(b, arm, p, (long)B, (const T*)q, (const T*)dq, (const T*)tg,
+                                               (const T*)tv, (T*)ie, (const T*)une, (T*)u, (T*)ts, scr);
     }
-#undef CALL
-#undef CALL1
-  }
-  return 0;
+    return 0;
+  });
 }
 // the six-row law in its two-pass, hand-over form (what libabrk launches for batches of up to 262144 rows): the first
 // pass compiled WITHOUT the eigen-decomposition (DeferOnly), a deferring row parks itself in the worklist and leaves its
@@ -100,40 +95,32 @@ int run_osc_handover(const A& arm, int n, const abrk_osc_params* P, int64_t B, c
                      const void* tg, const void* tv, void* ie, const void* une, void* u, void* ts,
                      int64_t* n_deferred) {
   OscP<T> p = make_oscp<T>(*P, n);
-  if (osc_fast_rows(*P, n, une != nullptr) != 0) return -1;
-  if (P->ki == 0) ie = nullptr;
-  const int feat = (tv || ie || une) ? 2 : (p.n_null > 0 ? 1 : 0);
+  const OscVariant v = variant_of(*P, p, n, tv, ie, une, ts, 0);
+  if (v.km != 6) return -1;
   const bool nulls = p.n_null > 0 || une != nullptr;
   // hand-over mode as on the device, rows one by one: the record of row b at rec[b] (the device packs a chunk's records
   // at the chunk's first slots - ScratchBase::record - and carries the row's index in the record); which rows deferred is
   // the kernel's business there (a ballot per 64-row chunk) and a plain flag array here
   std::vector<T> rec((size_t)B * rec_len(A::N), T(0));
   std::vector<char> flag((size_t)B, 0);
-  auto first = [&](long b, auto& scr, auto uc, auto ft) {
-    scr.allow_defer = true;
-    scr.rec_base = rec.data();
-    scr.handover = true;
-    scr.row = b;
-    osc_body<A, T, 6, uc(), ft()>(b, arm, p, (long)B, (const T*)q, (const T*)dq, (const T*)tg, (const T*)tv, (T*)ie,
-                                  (const T*)une, (T*)u, (T*)ts, scr);
-    flag[b] = scr.deferred;
-  };
-  using std::integral_constant;
-  for (long b = 0; b < B; b++) {
-    auto with_feat = [&](auto uc) {
-      if (feat == 0 && !ts) {
-        NoTs<DeferOnly<RegScratch<T, A::N>>> scr;
-        first(b, scr, uc, integral_constant<int, 0>{});
-      } else {
-        DeferOnly<RegScratch<T, A::N>> scr;
-        if (feat == 2) first(b, scr, uc, integral_constant<int, 2>{});
-        else if (feat == 1) first(b, scr, uc, integral_constant<int, 1>{});
-        else first(b, scr, uc, integral_constant<int, 0>{});
+  const int rc = with_variant<A, false>(v, [&](auto vt) {
+    using V = decltype(vt);
+    if constexpr (V::km == 6) {
+      for (long b = 0; b < B; b++) {
+        using S = DeferOnly<RegScratch<T, A::N>>;
+        std::conditional_t<V::nots, NoTs<S>, S> scr;
+        scr.allow_defer = true;
+        scr.rec_base = rec.data();
+        scr.handover = true;
+        scr.row = b;
+        osc_body<A, T, 6, V::use_c, V::feat>(b, arm, p, (long)B, (const T*)q, (const T*)dq, (const T*)tg, (const T*)tv,
+                                             (T*)ie, (const T*)une, (T*)u, (T*)ts, scr);
+        flag[b] = scr.deferred;
       }
-    };
-    if (P->use_C) with_feat(integral_constant<bool, true>{});
-    else with_feat(integral_constant<bool, false>{});
-  }
+    }
+    return 0;
+  });
+  if (rc != 0) return rc;
   int64_t total = 0;
   for (long b = 0; b < B; b++) {
     if (!flag[b]) continue;
@@ -146,15 +133,13 @@ int run_osc_handover(const A& arm, int n, const abrk_osc_params* P, int64_t B, c
   if (n_deferred) *n_deferred = total;
   return 0;
 }
-// the fused "u + Tx, J, M, g" row program (osc_full_body; FEAT 0 / 2 and KM 3 / 6 as Launch::osc_full dispatches)
+// the fused "u + Tx, J, M, g" row program (osc_full_body), the variant Launch::osc takes for `want`
 template <class A, class T>
 int run_osc_full(const A& arm, int n, const abrk_osc_params* P, int64_t B, const void* q, const void* dq,
                  const void* tg, const void* tv, void* ie, const void* une, void* u, void* ts, unsigned want,
                  void* const* outs) {
   OscP<T> p = make_oscp<T>(*P, n);
-  const int fast = osc_fast_rows(*P, n, une != nullptr);
-  if (P->ki == 0) ie = nullptr;
-  const bool plain = !(tv || ie || une) && p.n_null == 0;
+  const OscVariant v = variant_of(*P, p, n, tv, ie, une, ts, want);
   DynOutP<T> o{};
   o.Tx = (T*)outs[0];
   o.J = (T*)outs[1];
@@ -162,28 +147,16 @@ int run_osc_full(const A& arm, int n, const abrk_osc_params* P, int64_t B, const
   o.g = (T*)outs[3];
   o.C = (T*)outs[4];
   o.dJ = (T*)outs[5];
-  const bool vel = (want & (W_C | W_DJ)) != 0;
   DirectStore<T> st;
   RegScratch<T, A::N> scr;
-  for (long b = 0; b < B; b++) {
-#define FULL(KM, UC, FT, VEL)                                                                                            \
-  osc_full_body<A, T, KM, UC, FT, VEL>(b, true, st, arm, p, (long)B, (const T*)q, (const T*)dq, (const T*)tg, (const T*)tv, \
-                                       (T*)ie, (const T*)une, (T*)u, (T*)ts, want, o, scr)
-#define FULLF(KM, UC)                   \
-  do {                                  \
-    if (vel) FULL(KM, UC, 2, true);     \
-    else if (plain) FULL(KM, UC, 0, false); \
-    else FULL(KM, UC, 2, false);        \
-  } while (0)
-    if (fast == 3) {
-      if (P->use_C) FULLF(3, true); else FULLF(3, false);
-    } else {
-      if (P->use_C) FULLF(6, true); else FULLF(6, false);
-    }
-#undef FULLF
-#undef FULL
-  }
-  return 0;
+  return with_variant<A, true>(v, [&](auto vt) {
+    using V = decltype(vt);
+    for (long b = 0; b < B; b++)
+      osc_full_body<A, T, V::km, V::use_c, V::feat, V::vel>(b, true, st, arm, p, (long)B, (const T*)q, (const T*)dq,
+                                                            (const T*)tg, (const T*)tv, (T*)ie, (const T*)une, (T*)u,
+                                                            (T*)ts, want, o, scr);
+    return 0;
+  });
 }
 template <class A, class T>
 int run_sliding(const A& arm, int n, const abrk_sliding_params* P, int64_t B, const void* q, const void* dq,
@@ -216,41 +189,18 @@ int with_arm(const char* name, const abrk_arm_desc* d, int dtype, F&& f) {
 #endif
 #undef STATIC_CASE
   if (!d) return -4;
-#define RT_CASE(NN)                                                           \
-  if (d->n_joints == NN) {                                                    \
-    if (dtype == 0) {                                                         \
-      RtArm<NN, double> a;                                                    \
-      rt_fill<NN, double>(d, &a);                                             \
-      return f(a, double(0), NN);                                             \
-    } else {                                                                  \
-      RtArm<NN, float> a;                                                     \
-      rt_fill<NN, float>(d, &a);                                              \
-      return f(a, float(0), NN);                                              \
-    }                                                                         \
-  }
-#if HOSTSIM_RT_LO <= 1 && 1 <= HOSTSIM_RT_HI
-  RT_CASE(1)
-#endif
-#if HOSTSIM_RT_LO <= 2 && 2 <= HOSTSIM_RT_HI
-  RT_CASE(2)
-#endif
-#if HOSTSIM_RT_LO <= 3 && 3 <= HOSTSIM_RT_HI
-  RT_CASE(3)
-#endif
-#if HOSTSIM_RT_LO <= 4 && 4 <= HOSTSIM_RT_HI
-  RT_CASE(4)
-#endif
-#if HOSTSIM_RT_LO <= 5 && 5 <= HOSTSIM_RT_HI
-  RT_CASE(5)
-#endif
-#if HOSTSIM_RT_LO <= 6 && 6 <= HOSTSIM_RT_HI
-  RT_CASE(6)
-#endif
-#if HOSTSIM_RT_LO <= 7 && 7 <= HOSTSIM_RT_HI
-  RT_CASE(7)
-#endif
-#undef RT_CASE
-  return -4;
+  return for_joints(d->n_joints, [&](auto nn) {
+    constexpr int NN = decltype(nn)::value;
+    if constexpr (HOSTSIM_RT_LO <= NN && NN <= HOSTSIM_RT_HI) {
+      return for_dtype(dtype, [&](auto t) {
+        RtArm<NN, decltype(t)> a;
+        rt_fill<NN, decltype(t)>(d, &a);
+        return f(a, t, NN);
+      });
+    } else {
+      return -4;
+    }
+  }, -4);
 }
 }  // namespace
 
@@ -328,7 +278,7 @@ extern "C" int hostsim_obstacles(const char* builtin, const abrk_arm_desc* d, in
     using A = std::decay_t<decltype(a)>;
     using T = decltype(t);
     ObsP<T> p = make_obsp<T>(*P);
-    const bool split = !plain && A::kOrtho && A::N >= 3 && p.n * (A::N - 2) <= 64;
+    const bool split = !plain && obstacles_split<A>(p.n);
     for (long b = 0; b < B; b++) {
       if (split) obstacles_split_body<A, T>(b, a, p, (const T*)q, (T*)u, acc);
       else obstacles_body<A, T>(b, a, p, (const T*)q, (T*)u, acc);
@@ -357,39 +307,37 @@ extern "C" int hostsim_osc6_plan(int64_t B, unsigned given, const int64_t* sw, i
   return 0;
 }
 
+// the variant an OSC call takes (abrk_select.h `osc_variant`; integrated_error counts where ki != 0, as the host layer
+// stages it); out: km, use_c, feat, nots, full, vel
+extern "C" int hostsim_osc_variant(int fast, int n, int use_C, int n_null, int tv, int ki_nonzero, int ie, int une,
+                                   int ts, unsigned want, int* out) {
+  const OscVariant v = osc_variant(fast, n, use_C != 0, n_null, tv != 0, ki_nonzero && ie, une != 0, ts != 0, want);
+  out[0] = v.km;
+  out[1] = v.use_c;
+  out[2] = v.feat;
+  out[3] = v.nots;
+  out[4] = v.full;
+  out[5] = v.vel;
+  return 0;
+}
+
 extern "C" int hostsim_limits(int n, int dtype, const abrk_limits_params* P, int64_t B, const void* q, void* u,
                               int acc) {
-#define LIM_CASE(NN)                                                                                      \
-  if (n == NN) {                                                                                          \
-    if (dtype == 0) {                                                                                     \
-      LimitsP<double> p = make_limitsp<double>(*P);                                                       \
-      for (long b = 0; b < B; b++) limits_body<NN, double>(b, p, (const double*)q, (double*)u, acc);      \
-    } else {                                                                                              \
-      LimitsP<float> p = make_limitsp<float>(*P);                                                         \
-      for (long b = 0; b < B; b++) limits_body<NN, float>(b, p, (const float*)q, (float*)u, acc);         \
-    }                                                                                                     \
-    return 0;                                                                                             \
-  }
-  LIM_CASE(1) LIM_CASE(2) LIM_CASE(3) LIM_CASE(4) LIM_CASE(5) LIM_CASE(6) LIM_CASE(7)
-#undef LIM_CASE
-  return -1;
+  return for_joints_and_dtype(n, dtype, [&](auto nn, auto t) {
+    using T = decltype(t);
+    LimitsP<T> p = make_limitsp<T>(*P);
+    for (long b = 0; b < B; b++) limits_body<nn(), T>(b, p, (const T*)q, (T*)u, acc);
+    return 0;
+  }, -1);
 }
 
 extern "C" int hostsim_osc_mx(int n, int k, int dtype, int64_t B, const void* M, const void* J, double thr, void* Mx,
                               void* Minv) {
-#define MX_CASE(NN)                                                                                               \
-  if (n == NN) {                                                                                                  \
-    for (long b = 0; b < B; b++) {                                                                                \
-      if (dtype == 0)                                                                                             \
-        mx_body<NN, double>(b, k, thr, (const double*)M, (const double*)J, (double*)Mx, (double*)Minv);           \
-      else                                                                                                        \
-        mx_body<NN, float>(b, k, float(thr), (const float*)M, (const float*)J, (float*)Mx, (float*)Minv);         \
-    }                                                                                                             \
-    return 0;                                                                                                     \
-  }
-  MX_CASE(1) MX_CASE(2) MX_CASE(3) MX_CASE(4) MX_CASE(5) MX_CASE(6) MX_CASE(7)
-#undef MX_CASE
-  return -1;
+  return for_joints_and_dtype(n, dtype, [&](auto nn, auto t) {
+    using T = decltype(t);
+    for (long b = 0; b < B; b++) mx_body<nn(), T>(b, k, T(thr), (const T*)M, (const T*)J, (T*)Mx, (T*)Minv);
+    return 0;
+  }, -1);
 }
 // the direct symmetric 3x3 eigen-solver on its own (A: [B,3,3] symmetric; lam [B,3], V [B,3,3] columns = eigenvectors)
 // the 6 x 6 eigen-solvers behind the six-row law's truncating pinv: method 0 = cyclic Jacobi, 1 = Householder + QL
@@ -483,22 +431,18 @@ extern "C" int hostsim_sym3_eig(int dtype, int64_t B, const void* A, void* lam, 
   return 0;
 }
 extern "C" int hostsim_velocity_limiting(int dtype, const abrk_osc_params* P, int64_t B, const void* in, void* out) {
-  for (long b = 0; b < B; b++) {
-    if (dtype == 0)
-      velocity_limiting_body<double>(b, P->kp, P->ko, P->kv, P->vmax[0], P->vmax[1], (const double*)in, (double*)out);
-    else
-      velocity_limiting_body<float>(b, float(P->kp), float(P->ko), float(P->kv), float(P->vmax[0]), float(P->vmax[1]),
-                                    (const float*)in, (float*)out);
-  }
+  for_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    for (long b = 0; b < B; b++)
+      velocity_limiting_body<T>(b, T(P->kp), T(P->ko), T(P->kv), T(P->vmax[0]), T(P->vmax[1]), (const T*)in, (T*)out);
+  });
   return 0;
 }
 extern "C" int hostsim_orientation_forces(int alg, int dtype, int64_t B, const void* R, const void* abg, void* out) {
-  for (long b = 0; b < B; b++) {
-    if (dtype == 0)
-      orientation_forces_body<double>(b, alg, (const double*)R, (const double*)abg, (double*)out);
-    else
-      orientation_forces_body<float>(b, alg, (const float*)R, (const float*)abg, (float*)out);
-  }
+  for_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    for (long b = 0; b < B; b++) orientation_forces_body<T>(b, alg, (const T*)R, (const T*)abg, (T*)out);
+  });
   return 0;
 }
 
@@ -509,28 +453,15 @@ extern "C" int hostsim_osc_law(int n, int dtype, const abrk_osc_params* P, int64
   if (P->ki == 0) ie = nullptr;
   if (!P->use_g) g = nullptr;
   if (!P->use_C) c = nullptr;
-#define LAW_CASE(NN)                                                                                              \
-  if (n == NN) {                                                                                                  \
-    if (dtype == 0) {                                                                                             \
-      OscP<double> p = make_oscp<double>(*P, n);                                                                  \
-      for (long b = 0; b < B; b++)                                                                                \
-        osc_law_body<NN, double>(b, p, (long)B, (const double*)J, (const double*)M, (const double*)g,             \
-                                 (const double*)c, (const double*)xyz, (const double*)R, (const double*)q,        \
-                                 (const double*)dq, (const double*)tg, (const double*)tv, (double*)ie,            \
-                                 (const double*)une, (double*)u, (double*)ts);                                    \
-    } else {                                                                                                      \
-      OscP<float> p = make_oscp<float>(*P, n);                                                                    \
-      for (long b = 0; b < B; b++)                                                                                \
-        osc_law_body<NN, float>(b, p, (long)B, (const float*)J, (const float*)M, (const float*)g, (const float*)c, \
-                                (const float*)xyz, (const float*)R, (const float*)q, (const float*)dq,            \
-                                (const float*)tg, (const float*)tv, (float*)ie, (const float*)une, (float*)u,     \
-                                (float*)ts);                                                                      \
-    }                                                                                                             \
-    return 0;                                                                                                     \
-  }
-  LAW_CASE(1) LAW_CASE(2) LAW_CASE(3) LAW_CASE(4) LAW_CASE(5) LAW_CASE(6) LAW_CASE(7)
-#undef LAW_CASE
-  return -1;
+  return for_joints_and_dtype(n, dtype, [&](auto nn, auto t) {
+    using T = decltype(t);
+    OscP<T> p = make_oscp<T>(*P, n);
+    for (long b = 0; b < B; b++)
+      osc_law_body<nn(), T>(b, p, (long)B, (const T*)J, (const T*)M, (const T*)g, (const T*)c, (const T*)xyz,
+                            (const T*)R, (const T*)q, (const T*)dq, (const T*)tg, (const T*)tv, (T*)ie, (const T*)une,
+                            (T*)u, (T*)ts);
+    return 0;
+  }, -1);
 }
 
 #endif
@@ -544,18 +475,11 @@ extern "C" int hostsim_rollout(const char* builtin, const abrk_arm_desc* d, int 
     if constexpr (A::N == 2) {
       OscP<T> p = make_oscp<T>(*P, n);
       TwoLinkP<T> k{T(plant->K1), T(plant->K2), T(plant->K3), T(plant->K4), T(plant->dt)};
-      for (long b = 0; b < B; b++) {
-        const bool xy = osc_fast_rows(*P, n, false) == 2;
-#define ROLL(UC, KM)                                                                                            \
-  rollout_body<A, T, UC, KM>(b, a, p, k, (long)B, n_steps, every, (T*)q, (T*)dq, (const T*)tg, (T*)nullptr, (T*)qt, \
-                             (T*)dqt, (T*)ut)
-        if (xy) {
-          if (P->use_C) ROLL(true, 2); else ROLL(false, 2);
-        } else {
-          if (P->use_C) ROLL(true, 6); else ROLL(false, 6);
-        }
-#undef ROLL
-      }
+      with_rollout_variant(osc_fast_rows(*P, n, false), P->use_C != 0, [&](auto uc, auto km) {
+        for (long b = 0; b < B; b++)
+          rollout_body<A, T, uc(), km()>(b, a, p, k, (long)B, n_steps, every, (T*)q, (T*)dq, (const T*)tg, (T*)nullptr,
+                                         (T*)qt, (T*)dqt, (T*)ut);
+      });
       return 0;
     } else {
       return -1;

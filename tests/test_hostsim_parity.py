@@ -89,7 +89,7 @@ NOTS_CASES = [c for c in sorted(cases.CASES) if cases.takes_plain_six_row_law(c)
 
 def test_nots_case_list_covers_the_six_row_cases():
     """every golden case of the plain six-row law is run without the training signal too (the list is derived from the
-    dispatch rule, abrk_params.h osc_fast_rows + Launch::osc_launch_feat, not kept by hand)"""
+    dispatch rule, abrk_params.h osc_fast_rows + abrk_select.h osc_variant, not kept by hand)"""
     assert set(NOTS_CASES) == set(SIX_ROW_CASES)
 
 

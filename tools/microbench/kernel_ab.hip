@@ -1,5 +1,5 @@
 // Same-box A/B of ONE law of the product's kernels against a header directory (seconds to build instead of the library's
-// minutes): the OSC launch logic itself - abrk_kernels.h Launch::osc_launch<KM, USE_C, FEAT>, i.e. the same passes, grids
+// minutes): the OSC launch logic itself - abrk_kernels.h Launch::osc_launch_fixed<KM, USE_C, FEAT>, i.e. the same passes, grids
 // and worklist handling libabrk enqueues - compiled for one arm and one law, timed at several batch sizes.
 //
 //   build:  hipcc <library flags> -I<hdr-dir> -Iinclude -DAB_KM=6 -DAB_USE_C=0 -DAB_FEAT=0 [-DAB_ARM=Tab_jaco2] [-DAB_DOF5]
@@ -140,7 +140,7 @@ int main(int argc, char** argv) {
     }
     const LaunchArgs la{nullptr, B, st};
     auto step = [&]() {
-      CK((Launch<A, T>::template osc_launch<AB_KM, AB_USE_C != 0, AB_FEAT>(la, oa)));
+      CK((Launch<A, T>::template osc_launch_fixed<AB_KM, AB_USE_C != 0, AB_FEAT>(la, oa)));
       if (handover) CK(launch_osc6_finish(N, 0, la, fa));
     };
     step();
