@@ -346,6 +346,60 @@ def make_trace_params(frame, x_off=None, every=1, capacity=0, columns=("xyz", "e
     return p
 
 
+ADAPT_LIF, ADAPT_LIF_RATE = 0, 1  # ABRK_ADAPT_* (include/abrk.h)
+ADAPT_NEURON_TYPES = {"lif": ADAPT_LIF, "lif_rate": ADAPT_LIF_RATE}
+ADAPT_MAX_INPUT, ADAPT_MAX_OUTPUT = 64, 16
+ADAPT_TAU_PRE = 0.005
+
+
+class AdaptParams(C.Structure):
+    """abrk_adapt_params (include/abrk.h)"""
+    _fields_ = [("n_input", C.c_int32), ("n_output", C.c_int32), ("n_neurons_total", C.c_int32),
+                ("n_per_ensemble", C.c_int32), ("neuron_type", C.c_int32), ("dt", C.c_double),
+                ("tau_input", C.c_double), ("tau_training", C.c_double), ("tau_output", C.c_double),
+                ("tau_rc", C.c_double), ("tau_ref", C.c_double), ("pes_learning_rate", C.c_double)]
+
+
+class AdaptState(C.Structure):
+    """abrk_adapt_state (include/abrk.h): the seven per-row state arrays"""
+    _fields_ = [(k, C.c_void_p) for k in ("x_f", "e_f", "v", "ref", "a_f", "W", "out_f")]
+
+
+def make_adapt_params(n_input, n_output, n_neurons=1000, n_ensembles=1, neuron_type="lif", dt=0.001, tau_input=0.012,
+                      tau_training=0.012, tau_output=0.2, tau_rc=0.02, tau_ref=0.002, pes_learning_rate=1e-6):
+    """Parameters of engine.adapt_step: `n_ensembles` ensembles of `n_neurons` LIF neurons each ("lif": spiking,
+    "lif_rate": their rates; or the ABRK_ADAPT_* number) from n_input inputs to n_output outputs.  The defaults are the
+    reference's DynamicsAdaptation and Nengo's LIF.  The values are checked by the C entry point."""
+    p = AdaptParams()
+    p.n_input, p.n_output = int(n_input), int(n_output)
+    p.n_per_ensemble = int(n_neurons)
+    p.n_neurons_total = int(n_neurons) * int(n_ensembles)
+    if isinstance(neuron_type, str):
+        if neuron_type not in ADAPT_NEURON_TYPES:
+            raise ValueError(f"unknown neuron_type {neuron_type!r}: one of {tuple(ADAPT_NEURON_TYPES)}")
+        neuron_type = ADAPT_NEURON_TYPES[neuron_type]
+    p.neuron_type = int(neuron_type)
+    p.dt = float(dt)
+    p.tau_input, p.tau_training, p.tau_output = float(tau_input), float(tau_training), float(tau_output)
+    p.tau_rc, p.tau_ref = float(tau_rc), float(tau_ref)
+    p.pes_learning_rate = float(pes_learning_rate)
+    return p
+
+
+def lif_gain_bias(intercepts, max_rates, tau_rc=0.02, tau_ref=0.002):
+    """Nengo's LIF.gain_bias: the gain and bias with which a neuron starts firing at enc . x = intercept and fires at
+    max_rate at enc . x = 1.  With x = 1 / (1 - exp((tau_ref - 1 / max_rate) / tau_rc)): gain = (1 - x) / (intercept - 1),
+    bias = 1 - gain * intercept."""
+    intercepts, max_rates = np.asarray(intercepts, dtype=float), np.asarray(max_rates, dtype=float)
+    if np.any(max_rates >= 1.0 / tau_ref):
+        raise ValueError(f"max_rates must be below 1 / tau_ref = {1.0 / tau_ref:g}")
+    if np.any(intercepts >= 1.0):
+        raise ValueError("intercepts must be below 1")
+    x = 1.0 / (1.0 - np.exp((tau_ref - 1.0 / max_rates) / tau_rc))
+    gain = (1.0 - x) / (intercepts - 1.0)
+    return gain, 1.0 - gain * intercepts
+
+
 TABLE_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "arms", "tables")
 BUILTIN_ARMS = ("ur5", "jaco2", "twojoint", "threejoint", "onejoint")
 

@@ -26,6 +26,7 @@
 #include "abrk_kernels.h"
 #include "abrk_params.h"
 #include "abrk_path.h"
+#include "abrk_adapt.h"
 
 namespace abrk {
 const ArmOps* ops_ur5();
@@ -2360,6 +2361,106 @@ extern "C" int abrk_path_next_batch(int dtype, int64_t B, int32_t t_max, int32_t
   na.W = width;
   const hipStream_t hs = (hipStream_t)stream;
   return dispatch(st, nullptr, dtype, [=](const void*) { return launch_path_next(dtype, na, hs); });
+}
+
+// ------------------------------------------------------------------------------- adaptive signal
+namespace {
+template <class T>
+AdaptArgs<T> make_adapt_args(const abrk_adapt_params& P, int64_t B, int w0, int w1) {
+  return adapt_make_args<T>(P.n_input, P.n_output, P.n_neurons_total, P.n_per_ensemble, w0, w1, (long)B, P.dt, P.tau_input,
+                            P.tau_training, P.tau_output, P.tau_rc, P.tau_ref, P.pes_learning_rate);
+}
+
+// the arrays of one call, bound once in void form and handed to the typed block
+struct AdaptPtrs {
+  const void *enc, *gain, *bias, *shift, *scale, *in0, *in1, *training;
+  void *x_f, *e_f, *v, *ref, *a_f, *W, *out_f, *out, *u_add;
+};
+template <class T>
+AdaptArgs<T> bind_adapt(AdaptArgs<T> a, const AdaptPtrs& p) {
+  a.enc = (const T*)p.enc;
+  a.gain = (const T*)p.gain;
+  a.bias = (const T*)p.bias;
+  a.shift = (const T*)p.shift;
+  a.scale = (const T*)p.scale;
+  a.in0 = (const T*)p.in0;
+  a.in1 = (const T*)p.in1;
+  a.training = (const T*)p.training;
+  a.x_f = (T*)p.x_f;
+  a.e_f = (T*)p.e_f;
+  a.v = (T*)p.v;
+  a.ref = (T*)p.ref;
+  a.a_f = (T*)p.a_f;
+  a.W = (T*)p.W;
+  a.out_f = (T*)p.out_f;
+  a.out = (T*)p.out;
+  a.u_add = (T*)p.u_add;
+  return a;
+}
+}  // namespace
+
+extern "C" int abrk_adapt_step_batch(int dtype, const abrk_adapt_params* P, int64_t B, const void* enc, const void* gain,
+                                     const void* bias, const void* shift, const void* scale, const void* in0, int32_t w0,
+                                     const void* in1, int32_t w1, const void* training, const abrk_adapt_state* S,
+                                     void* out, void* u_add, int device, void* stream) {
+  if (dtype != ABRK_F64 && dtype != ABRK_F32) return fail(ABRK_EINVAL, "dtype %d is not ABRK_F64/ABRK_F32", dtype);
+  if (!P || !S) return fail(ABRK_EINVAL, "params and state are required");
+  if (B < 0 || B > 2147483647) return fail(ABRK_EINVAL, "batch %lld outside 0..2^31-1", (long long)B);
+  if (P->neuron_type != ABRK_ADAPT_LIF && P->neuron_type != ABRK_ADAPT_LIF_RATE)
+    return fail(ABRK_EINVAL, "neuron_type %d is not ABRK_ADAPT_LIF/ABRK_ADAPT_LIF_RATE", P->neuron_type);
+  if (P->n_input < 1 || P->n_input > ABRK_ADAPT_MAX_INPUT)
+    return fail(ABRK_EINVAL, "n_input=%d outside 1..%d", P->n_input, ABRK_ADAPT_MAX_INPUT);
+  if (P->n_output < 1 || P->n_output > ABRK_ADAPT_MAX_OUTPUT)
+    return fail(ABRK_EINVAL, "n_output=%d outside 1..%d", P->n_output, ABRK_ADAPT_MAX_OUTPUT);
+  if (P->n_neurons_total < 1) return fail(ABRK_EINVAL, "n_neurons_total=%d < 1", P->n_neurons_total);
+  if (P->n_per_ensemble < 1) return fail(ABRK_EINVAL, "n_per_ensemble=%d < 1", P->n_per_ensemble);
+  if ((int64_t)P->n_neurons_total * P->n_output > 2147483647)
+    return fail(ABRK_EINVAL, "n_neurons_total * n_output = %lld weights per row exceed 2^31-1",
+                (long long)P->n_neurons_total * P->n_output);
+  if (w0 < 1 || w1 < 0 || (int64_t)w0 + w1 != P->n_input)
+    return fail(ABRK_EINVAL, "input widths %d + %d do not make n_input=%d", w0, w1, P->n_input);
+  if (!positive_finite_at(&P->dt)) return fail(ABRK_EINVAL, "dt=%g is not a positive finite step", P->dt);
+  if (!positive_finite_at(&P->tau_rc)) return fail(ABRK_EINVAL, "tau_rc=%g is not positive and finite", P->tau_rc);
+  if (!nonnegative_finite_at(&P->tau_ref) || !nonnegative_finite_at(&P->tau_input) ||
+      !nonnegative_finite_at(&P->tau_training) || !nonnegative_finite_at(&P->tau_output) ||
+      !nonnegative_finite_at(&P->pes_learning_rate))
+    return fail(ABRK_EINVAL, "a time constant or pes_learning_rate is negative or not finite");
+  const bool lif = P->neuron_type == ABRK_ADAPT_LIF;
+  if (!enc || !gain || !bias || !shift || !scale) return fail(ABRK_EINVAL, "enc, gain, bias, shift and scale are required");
+  if (!in0 || (w1 > 0 && !in1)) return fail(ABRK_EINVAL, "in0 is required, and in1 when w1 > 0");
+  if (!training || !out) return fail(ABRK_EINVAL, "training and out are required");
+  if (!S->x_f || !S->e_f || !S->a_f || !S->W || !S->out_f || (lif && (!S->v || !S->ref)))
+    return fail(ABRK_EINVAL, "a state array is NULL (x_f, e_f, a_f, W, out_f; v and ref for ABRK_ADAPT_LIF)");
+  if (B == 0) return 0;
+  if (int rc = use_device(device)) return rc;
+  const size_t s = esz(dtype), D = (size_t)P->n_input, O = (size_t)P->n_output, N = (size_t)P->n_neurons_total;
+  Stager st{device, (hipStream_t)stream};
+  AdaptPtrs p{};
+  st.in(&p.enc, enc, N * D * s);
+  st.in(&p.gain, gain, N * s);
+  st.in(&p.bias, bias, N * s);
+  st.in(&p.shift, shift, D * s);
+  st.in(&p.scale, scale, D * s);
+  st.in(&p.in0, in0, (size_t)B * w0 * s);
+  st.in(&p.in1, w1 > 0 ? in1 : nullptr, (size_t)B * w1 * s);
+  st.in(&p.training, training, (size_t)B * O * s);
+  st.inout(&p.x_f, S->x_f, (size_t)B * D * s);
+  st.inout(&p.e_f, S->e_f, (size_t)B * O * s);
+  st.inout(&p.v, lif ? S->v : nullptr, (size_t)B * N * s);
+  st.inout(&p.ref, lif ? S->ref : nullptr, (size_t)B * N * s);
+  st.inout(&p.a_f, S->a_f, (size_t)B * N * s);
+  st.inout(&p.W, S->W, (size_t)B * O * N * s);
+  st.inout(&p.out_f, S->out_f, (size_t)B * O * s);
+  st.out(&p.out, out, (size_t)B * O * s);
+  st.inout(&p.u_add, u_add, (size_t)B * O * s);
+  if (int rc = st.reserve()) return rc;
+  const int type = lif ? kAdaptLif : kAdaptLifRate;
+  const AdaptArgs<double> a64 = bind_adapt(make_adapt_args<double>(*P, B, w0, w1), p);
+  const AdaptArgs<float> a32 = bind_adapt(make_adapt_args<float>(*P, B, w0, w1), p);
+  const hipStream_t hs = (hipStream_t)stream;
+  return dispatch(st, nullptr, dtype, [=](const void*) {
+    return dtype == ABRK_F64 ? launch_adapt_step(type, a64, hs) : launch_adapt_step(type, a32, hs);
+  });
 }
 
 // ------------------------------------------------------------------------------- launch plans

@@ -724,6 +724,43 @@ def loop_trace(arm_id, n, params, q, dq, u, target, counter, history=None, stats
                                       _sp(stream)))
 
 
+ADAPT_STATE = ("x_f", "e_f", "v", "ref", "a_f", "W", "out_f")
+
+
+def adapt_state_shapes(params, B):
+    """{name: shape} of the per-row state of engine.adapt_step for B rows"""
+    D, O, N = int(params.n_input), int(params.n_output), int(params.n_neurons_total)
+    return {"x_f": (B, D), "e_f": (B, O), "v": (B, N), "ref": (B, N), "a_f": (B, N), "W": (B, O, N), "out_f": (B, O)}
+
+
+def adapt_step(params, enc, gain, bias, shift, scale, in0, training, state, in1=None, out=None, u_add=None,
+               dtype=np.float64, device=0, stream=None):
+    """One tick of the adaptive signal (abrk_adapt_step_batch) - recordable into a Plan.  params: _abi.make_adapt_params.
+    enc [N,D], gain [N], bias [N], shift [D], scale [D] are shared by the rows; the row's input is concat(in0[b], in1[b])
+    ([B,w0], [B,w1] with w0 + w1 = D: q and dq of a loop); training [B,O].  state: a dict of the seven arrays of
+    adapt_state_shapes (v and ref may be missing for "lif_rate"), updated in place.  -> out [B,O], the filtered output;
+    u_add [B,O], when given, has it added.  All arrays are of `dtype`, NumPy or DeviceArray alike."""
+    a = _Args(dtype)
+    D, O, N = int(params.n_input), int(params.n_output), int(params.n_neurons_total)
+    B = in0.shape[0]
+    w0 = in0.shape[1]
+    w1 = 0 if in1 is None else in1.shape[1]
+    i0p, i1p = a.inp(in0, (B, w0), "in0"), a.inp(in1, (B, w1), "in1")
+    tp = a.inp(training, (B, O), "training")
+    tabs = [a.inp(x, sh, nm) for x, sh, nm in ((enc, (N, D), "enc"), (gain, (N,), "gain"), (bias, (N,), "bias"),
+                                               (shift, (D,), "shift"), (scale, (D,), "scale"))]
+    st = _abi.AdaptState()
+    for name, shape in adapt_state_shapes(params, B).items():
+        arr = state.get(name)
+        if arr is not None:
+            setattr(st, name, _inout(a, arr, shape, name))
+    up = None if u_add is None else _inout(a, u_add, (B, O), "u_add")
+    op, oo = a.out(out, (B, O), device, "out")
+    check(lib().abrk_adapt_step_batch(a.code, C.byref(params), B, *tabs, i0p, w0, i1p, w1, tp, C.byref(st), op, up,
+                                      device, _sp(stream)))
+    return oo
+
+
 class Plan:
     """One control tick recorded as a launch plan (abrk_plan_begin .. abrk_plan_end): every engine call made inside
     the `with` block - on DeviceArrays, with this plan's device and stream - is validated and converted once and its

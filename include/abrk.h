@@ -476,6 +476,62 @@ int abrk_path_next_batch(int dtype, int64_t B, int32_t t_max, int32_t width, con
                          void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * The adaptive signal of a recorded loop: what the reference's controllers/signals/DynamicsAdaptation
+ * (abr_control/controllers/signals/dynamics_adaptation.py) builds out of Nengo - ensembles of LIF neurons over the
+ * scaled joint state whose decoders learn by PES from the controller's training_signal - for B independent rows, one
+ * tick per call.  N = n_neurons_total neurons (all ensembles side by side), D = n_input, O = n_output.
+ * Shared by the rows, of `dtype`: enc [N,D] (unit rows), gain [N], bias [N], shift [D], scale [D].
+ * Per row, of `dtype`, read and written by every call (abrk_adapt_state): x_f [B,D], e_f [B,O], v [B,N], ref [B,N],
+ * a_f [B,N], W [B,O,N] (neuron index contiguous), out_f [B,O].  Zero filling all seven restarts the rows.
+ * With a(tau) = 1 - exp(-dt / tau), a(0) = 1, one tick of row b is
+ *   1  x = (concat(in0[b], in1[b]) - shift) * scale;  x_f += a(tau_input) (x - x_f)     in0 [B,w0], in1 [B,w1] or NULL
+ *   2  e_f += a(tau_training) (training[b] - e_f)                                          training [B,O]
+ *   3  J_i = gain_i (enc_i . x_f) + bias_i, then per neuron
+ *        ABRK_ADAPT_LIF       ref -= dt;  d = clip(dt - ref, 0, dt);  v -= (J - v) expm1(-d / tau_rc);  on v > 1:
+ *                             t_s = dt + tau_rc log1p(-(v - 1) / (J - 1)), v = 0, ref = tau_ref + t_s, s = 1 / dt;
+ *                             otherwise v = max(v, 0), s = 0
+ *        ABRK_ADAPT_LIF_RATE  s = 1 / (tau_ref + tau_rc log1p(1 / (J - 1))) for J > 1, else 0   (v, ref are not touched
+ *                             and may be NULL)
+ *   4  y_o = sum_i W[o,i] s_i                          (the weights from before this tick's update)
+ *   5  out_f += a(tau_output) (y - out_f);  out[b] = out_f;  u_add[b] += out_f              out, u_add [B,O]; u_add or NULL
+ *   6  a_f,i += a(ABRK_ADAPT_TAU_PRE) (s_i - a_f,i)
+ *   7  W[o,i] += (pes_learning_rate dt / n_per_ensemble) e_f[o] a_f,i
+ * (the reference feeds -training_signal as the error and PES subtracts: the two signs cancel).  These are Nengo's published
+ * Lowpass, LIF / LIFRate and PES operators; their order within a tick is this library's, and agreement with Nengo's
+ * simulator to the tick is not claimed.
+ * Goes through the staging of every *_batch call (host arrays work for one-off calls) and is recorded between
+ * abrk_plan_begin and abrk_plan_end: in { law(training_signal = ts); adapt(q, dq, ts, u_add = u); plant step } the state
+ * lives in device memory and advances at every replay.
+ * ABRK_EINVAL: dtype, neuron_type, B < 0, n_input outside 1..ABRK_ADAPT_MAX_INPUT, n_output outside
+ * 1..ABRK_ADAPT_MAX_OUTPUT, n_neurons_total < 1, n_per_ensemble < 1, w0 + w1 != n_input (w1 != 0 with in1 NULL), a dt, tau_rc
+ * that is not positive and finite, another time constant or pes_learning_rate that is negative or not finite, a NULL
+ * required array.
+ * --------------------------------------------------------------------------------- */
+#define ABRK_ADAPT_LIF 0
+#define ABRK_ADAPT_LIF_RATE 1
+#define ABRK_ADAPT_MAX_INPUT 64
+#define ABRK_ADAPT_MAX_OUTPUT 16
+#define ABRK_ADAPT_TAU_PRE 0.005
+typedef struct abrk_adapt_params {
+  int32_t n_input;         /* D */
+  int32_t n_output;        /* O */
+  int32_t n_neurons_total; /* N = n_ensembles * n_per_ensemble */
+  int32_t n_per_ensemble;
+  int32_t neuron_type;     /* ABRK_ADAPT_LIF | ABRK_ADAPT_LIF_RATE */
+  double dt;
+  double tau_input, tau_training, tau_output; /* 0: no filter */
+  double tau_rc, tau_ref;                     /* Nengo's LIF defaults: 0.02, 0.002 */
+  double pes_learning_rate;
+} abrk_adapt_params;
+typedef struct abrk_adapt_state {
+  void *x_f, *e_f, *v, *ref, *a_f, *W, *out_f;
+} abrk_adapt_state;
+int abrk_adapt_step_batch(int dtype, const abrk_adapt_params* params, int64_t B, const void* enc, const void* gain,
+                          const void* bias, const void* shift, const void* scale, const void* in0, int32_t w0,
+                          const void* in1, int32_t w1, const void* training, const abrk_adapt_state* state, void* out,
+                          void* u_add, int device, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * The output side of a recorded loop: what every closed-loop example of the reference keeps in ee_track / target_track /
  * q_track lists and reduces with np.linalg.norm(ee - target), kept on the device.  One call = one tick of every row.  With
  * t = counter[b]:
