@@ -26,9 +26,7 @@ class Joint(Controller):
         return _abi.make_joint(self.kp, self.kv)
 
     def generate(self, q, dq, target, target_velocity=None):
-        rc = self.robot_config
-        (q2, dq2, t2, tv2), single = self._rows(q, dq, target, target_velocity)
-        u = self._joint_generate(self._ctrl(), self.account_for_gravity, q2, dq2, t2, tv2)
-        if isinstance(u, np.ndarray) and rc.reference_dtypes:
-            u = u.astype(np.float64)
-        return u[0] if single else u
+        return self._generate(None, q, dq, target, target_velocity)
+
+    def _generate(self, where, q, dq, target, target_velocity=None):
+        return self._joint_generate(where, self._ctrl(), self.account_for_gravity, q, dq, target, target_velocity)

@@ -5,6 +5,7 @@ import numpy as np
 
 from .. import _abi, engine
 from .._lib import DeviceArray
+from ..sharding import ShardedArray
 from .controller import Controller
 from .damping import Damping
 from .resting_config import RestingConfig
@@ -159,23 +160,31 @@ class OSC(Controller):
         q, dq: (n,) or (B, n); target: (6,) or (B, 6) [x,y,z,alpha,beta,gamma];
         target_velocity: None, (6,) or (B, 6).  Returns float64 (n,) or (B, n)
         (kernel dtype for a float32 config / DeviceArrays)."""
+        return self._generate(None, q, dq, target, target_velocity, ref_frame, xyz_offset, return_dynamics)
+
+    @staticmethod
+    def _fused_only(ctrlr, what):
+        """what runs over several devices is the fused kernel alone: null controllers summed by kernels of their own or
+        evaluated on the host, and a foreign config's dynamics, stay with the one-device generate()"""
+        if not isinstance(ctrlr, OSC) or not ctrlr._fused_config or ctrlr._foreign or ctrlr._device:
+            raise TypeError(f"{what} needs an abr_control_amd OSC with fused null controllers only")
+
+    def _generate(self, where, q, dq, target, target_velocity=None, ref_frame="EE", xyz_offset=None, return_dynamics=None,
+                  u=None):
         rc = self.robot_config
+        if where is not None:
+            self._fused_only(self, "MultiDevice.generate")
+            if return_dynamics:
+                raise TypeError("return_dynamics: the fused robot_config outputs come from the one-device call only")
         if not self._fused_config:
             if return_dynamics:
                 raise TypeError("return_dynamics needs an abr_control_amd arm config (a foreign config's J/M/g are its own)")
             return self._generate_foreign(q, dq, target, target_velocity, ref_frame, xyz_offset)
         params = self._params(ref_frame, xyz_offset)
         (q2, dq2, t2, tv2), single = self._rows(q, dq, target, target_velocity)
-        on_device = isinstance(q2, DeviceArray)
+        on_device = not isinstance(q2, np.ndarray)
         B = q2.shape[0]
-        ie = None
-        if self.ki != 0:  # per-row state (osc.py:81-82, 262-264)
-            ie = self.integrated_error
-            if on_device:
-                if not isinstance(ie, DeviceArray) or ie.shape != (B, 6):
-                    ie = self.integrated_error = DeviceArray((B, 6), rc.dtype, rc.device).zero_()
-            else:
-                ie = self._host_integrated_error(B, rc.dtype)
+        ie = self._integral_state(q2)
         une = None
         if self._foreign:
             if on_device:
@@ -192,12 +201,11 @@ class OSC(Controller):
                 nc._accumulate(q2, dq2, une)
         dyn = None
         if return_dynamics:
-            u, ts, dyn = engine.osc_generate(rc.arm_id, rc.N_JOINTS, params, q2, dq2, t2, tv2, ie, une,
-                                             training_signal=True, dtype=rc.dtype, device=rc.device,
-                                             want=tuple(return_dynamics))
+            u, ts, dyn = engine.osc_generate(rc.arm_id, rc.N_JOINTS, params, q2, dq2, t2, tv2, ie, une, u, True, rc.dtype,
+                                             rc.device, want=tuple(return_dynamics))
         else:
-            u, ts = engine.osc_generate(rc.arm_id, rc.N_JOINTS, params, q2, dq2, t2, tv2, ie, une,
-                                        training_signal=True, dtype=rc.dtype, device=rc.device)
+            u, ts = engine._osc(self._marshal(where, q2), rc.arm_id, rc.N_JOINTS, params, q2, dq2, t2, tv2, ie, une, u,
+                                True)
         if on_device:
             self.training_signal = ts
             return (u, dyn) if dyn is not None else u
@@ -210,6 +218,22 @@ class OSC(Controller):
             dyn = {k: (v[0] if single else v) for k, v in dyn.items()}
             return (u[0] if single else u), dyn
         return u[0] if single else u
+
+    def _integral_state(self, q2):
+        """the per-row state (osc.py:81-82, 262-264) of a call on q2's rows, living where q2 lives: on the host (below),
+        or a DeviceArray / ShardedArray that stays in self.integrated_error and starts from zero"""
+        if self.ki == 0:
+            return None
+        rc = self.robot_config
+        B, ie = q2.shape[0], self.integrated_error
+        if isinstance(q2, np.ndarray):
+            return self._host_integrated_error(B, rc.dtype)
+        if isinstance(q2, ShardedArray):
+            if not isinstance(ie, ShardedArray) or ie.shape != (B, 6) or ie.devices != q2.devices:
+                ie = self.integrated_error = ShardedArray.zeros((B, 6), rc.dtype, q2.devices)
+        elif not isinstance(ie, DeviceArray) or ie.shape != (B, 6):
+            ie = self.integrated_error = DeviceArray((B, 6), rc.dtype, rc.device).zero_()
+        return ie
 
     def _host_integrated_error(self, B, dtype):
         """the per-row integral state (osc.py:81-82, 262-264) as the [B, 6] array a call updates in place: a single

@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _abi
 from ._lib import NP_DTYPE, AbrkError, DeviceArray, check, lib  # noqa: F401
+from .sharding import ShardedArray
 
 _OUT_SHAPES = {
     "Tx": lambda n: (3,),
@@ -39,78 +40,278 @@ def _dtype_code(dtype):
     raise TypeError(f"abr_control_amd computes in float64 or float32, not {dt}")
 
 
-class _Args:
-    """Marshals array arguments: keeps host copies alive, decides host/device mode."""
+# (np.dtype, ABRK_F64 / ABRK_F32) of the spellings callers use, looked up once per call; any other goes the long way
+_DTYPES = {k: (np.dtype(k), _dtype_code(k)) for t in (np.float64, np.float32) for k in (t, np.dtype(t))}
 
-    def __init__(self, dtype):
-        self.np_dtype = np.dtype(dtype)
-        self.code = _dtype_code(dtype)
-        self.keep = []
-        self.on_device = None
 
-    def _mode(self, dev):
-        if self.on_device is None:
-            self.on_device = dev
-        elif self.on_device != dev:
-            raise TypeError("mixing DeviceArray and NumPy arguments in one call is not supported")
-
-    def inp(self, a, shape, name):
-        if a is None:
-            return None
-        if isinstance(a, DeviceArray):
-            self._mode(True)
-            if a.dtype != self.np_dtype or a.shape != tuple(shape):
-                raise ValueError(f"{name}: expected {self.np_dtype}{tuple(shape)}, got {a.dtype}{a.shape}")
-            return a.ptr
-        self._mode(False)
-        h = np.ascontiguousarray(a, dtype=self.np_dtype)
-        if h.shape != tuple(shape):
-            raise ValueError(f"{name}: expected shape {tuple(shape)}, got {h.shape}")
-        self.keep.append(h)
-        return h.ctypes.data
-
-    def out(self, given, shape, device, name):
-        """-> (pointer, object to return)"""
-        if self.on_device:
-            if given is None:
-                given = DeviceArray(shape, self.np_dtype, device)
-            elif not isinstance(given, DeviceArray) or given.shape != tuple(shape) or given.dtype != self.np_dtype:
-                raise ValueError(f"{name}: output must be a DeviceArray {self.np_dtype}{tuple(shape)}")
-            return given.ptr, given
-        if given is None:
-            given = np.empty(shape, self.np_dtype)
-        elif (not isinstance(given, np.ndarray) or given.shape != tuple(shape) or given.dtype != self.np_dtype
-              or not given.flags.c_contiguous):
-            raise ValueError(f"{name}: output must be a C-contiguous ndarray {self.np_dtype}{tuple(shape)}")
-        return given.ctypes.data, given
+def _dtype_of(dtype):
+    return _DTYPES.get(dtype) or (np.dtype(dtype), _dtype_code(dtype))
 
 
 def _sp(stream):
     return None if stream is None else getattr(stream, "ptr", stream)
 
 
+class _Marshal:
+    """What every marshaller of array arguments offers, wherever the call runs (one device: _Args; one host batch over
+    several devices: _HostBatch; shards resident on devices: _Cut).  inp / out / inout / side bind an input, an output
+    (-> pointer, object to return), a state array updated in place and an int32 or float64 side array; shapes are the
+    whole batch's, [B, ...], as tuples.  `form` names the C entry (abrk_<family>_<form>), `batch(B)` is what that entry
+    takes for the batch (the row count, or the cut) and `where` its trailing arguments."""
+
+    def opt_out(self, flag, shape, name):
+        """an output the caller may leave out: False / None (-> None, None), True (allocated here) or the array"""
+        if flag is None or flag is False:
+            return None, None
+        return self.out(None if flag is True else flag, shape, name)
+
+    def want(self, names, n, B, out=None, offered=None):
+        """the robot_config outputs `names` -> (ABRK_WANT_* bits, the abrk_dyn_out argument, {name: array}); `out`: a
+        dict of preallocated arrays"""
+        bits, ptrs, res = 0, {}, {}
+        for name in names:
+            if offered is not None and name not in offered:
+                raise ValueError(f"the fused kernel offers {', '.join(offered)} - not {name!r}")
+            bits |= _WANT_BITS[name]
+            ptrs[name], res[name] = self.out(None if out is None else out.get(name), (B,) + _OUT_SHAPES[name](n), name)
+        return bits, self._dyn_out(ptrs), res
+
+
+class _Args(_Marshal):
+    """One device: NumPy arrays (staged by the library; host copies are kept alive here) or DeviceArrays, not both."""
+    form = "batch"
+    on_device = None  # decided by the first array
+    mixed = "mixing DeviceArray and NumPy arguments in one call is not supported"
+
+    def __init__(self, dtype, device=0, stream=None):
+        self.np_dtype, self.code = _dtype_of(dtype)
+        self.keep = []
+        self.device = device
+        self.where = (device, _sp(stream))
+
+    def batch(self, B):
+        return B
+
+    def _mode(self, dev, name):
+        if self.on_device is None:
+            self.on_device = dev
+        elif self.on_device != dev:
+            raise TypeError(f"{name}: {self.mixed}")
+
+    def inp(self, a, shape, name):
+        if a is None:
+            return None
+        if isinstance(a, DeviceArray):
+            if self.on_device is not True:
+                self._mode(True, name)
+            if a.dtype != self.np_dtype or a.shape != shape:
+                raise ValueError(f"{name}: expected {self.np_dtype}{shape}, got {a.dtype}{a.shape}")
+            return a.ptr
+        if self.on_device is not False:
+            self._mode(False, name)
+        h = np.ascontiguousarray(a, dtype=self.np_dtype)
+        if h.shape != shape:
+            raise ValueError(f"{name}: expected shape {shape}, got {h.shape}")
+        self.keep.append(h)
+        return h.ctypes.data
+
+    def out(self, given, shape, name):
+        if self.on_device:
+            if given is None:
+                given = DeviceArray(shape, self.np_dtype, self.device)
+            elif not isinstance(given, DeviceArray) or given.shape != shape or given.dtype != self.np_dtype:
+                raise ValueError(f"{name}: output must be a DeviceArray {self.np_dtype}{shape}")
+            return given.ptr, given
+        if given is None:
+            given = np.empty(shape, self.np_dtype)
+        elif (not isinstance(given, np.ndarray) or given.shape != shape or given.dtype != self.np_dtype
+              or not given.flags.c_contiguous):
+            raise ValueError(f"{name}: output must be a C-contiguous ndarray {self.np_dtype}{shape}")
+        return given.ctypes.data, given
+
+    def inout(self, arr, shape, name):
+        """a DeviceArray, or a C-contiguous ndarray of the call dtype: it is written, so no copy may stand in for it"""
+        if arr is None:
+            return None
+        if isinstance(arr, DeviceArray):
+            return self.inp(arr, shape, name)
+        if (not isinstance(arr, np.ndarray) or arr.dtype != self.np_dtype or arr.shape != shape
+                or not arr.flags.c_contiguous):
+            raise ValueError(f"{name} must be a C-contiguous ndarray {shape} of the call dtype (updated in place)")
+        self._mode(False, name)
+        return arr.ctypes.data
+
+    def side(self, arr, shape, name, dtype=np.int32):
+        """an array of a dtype of its own (int32 counters, float64 statistics), passed as it is"""
+        dev = isinstance(arr, DeviceArray)
+        self._mode(dev, name)
+        if arr.dtype != dtype or tuple(arr.shape) != shape or (not dev and not arr.flags.c_contiguous):
+            raise ValueError(f"{name}: expected a C-contiguous {np.dtype(dtype)} array {shape}, "
+                             f"got {arr.dtype}{tuple(arr.shape)}")
+        return arr.ptr if dev else arr.ctypes.data
+
+    def _dyn_out(self, ptrs):
+        return C.byref(_abi.DynOut(**ptrs))
+
+
+class _HostBatch(_Args):
+    """ONE host batch cut into contiguous row shards, shard g on devices[g]: NumPy arrays only."""
+    form = "sharded"
+    on_device = False
+    mixed = "the sharded calls take NumPy arrays (a DeviceArray lives on one device)"
+
+    def __init__(self, dtype, devices):
+        _Args.__init__(self, dtype)
+        self.where = (len(devices), (C.c_int * len(devices))(*[int(d) for d in devices]))
+
+    def out(self, given, shape, name):
+        self._mode(isinstance(given, DeviceArray), name)
+        return _Args.out(self, given, shape, name)
+
+    def inout(self, arr, shape, name):
+        self._mode(isinstance(arr, DeviceArray), name)
+        return _Args.inout(self, arr, shape, name)
+
+
+class _PlanArgs(_Args):
+    """The fixed buffers of a launch plan: DeviceArrays only, the outputs too."""
+    on_device = True
+    mixed = "launch plans take DeviceArrays"
+
+    def out(self, given, shape, name):
+        self._mode(isinstance(given, DeviceArray), name)
+        return _Args.out(self, given, shape, name)
+
+    inout = _Args.inp
+
+
+class _Cut(_Marshal):
+    """Shards resident on devices: abrk_shard_cut + the per-shard pointer tables of one call, whose arrays
+    are sharding.ShardedArrays cut like `like`; shard g runs on streams[g], or on the library's own stream of its
+    (device, slot)."""
+    form, where = "resident", ()
+
+    def __init__(self, like, dtype, streams=None):
+        self.devices, self.rows = list(like.devices), list(like.rows)
+        self.G = len(self.devices)
+        self.np_dtype, self.code = _dtype_of(dtype)
+        self._dev = (C.c_int32 * self.G)(*self.devices)
+        self._rows = (C.c_int64 * self.G)(*self.rows)
+        self._streams = None
+        if streams is not None:
+            if len(streams) != self.G:
+                raise ValueError(f"{len(streams)} streams for {self.G} shards")
+            self._streams = (C.c_void_p * self.G)(*[_sp(st) for st in streams])
+        self.c = _abi.ShardCut(self.G, self._dev, self._rows, self._streams)
+
+    def batch(self, B):
+        return C.byref(self.c)
+
+    def inp(self, arr, shape, name, dtype=None):
+        """pointer table of a ShardedArray (None -> NULL), checked against the cut"""
+        if arr is None:
+            return None
+        if list(arr.devices) != self.devices or list(arr.rows) != self.rows:
+            raise ValueError(f"{name}: cut over other devices / rows than q")
+        if arr.dtype != (dtype or self.np_dtype) or tuple(arr.shape) != tuple(shape):
+            raise ValueError(f"{name}: expected {np.dtype(dtype or self.np_dtype)}{tuple(shape)}, got {arr.dtype}{arr.shape}")
+        return (C.c_void_p * self.G)(*[p.ptr for p in arr.parts])
+
+    inout = inp
+
+    def side(self, arr, shape, name, dtype=np.int32):
+        return self.inp(arr, shape, name, dtype)
+
+    def out(self, given, shape, name):
+        if given is None:
+            given = ShardedArray.empty(shape, self.np_dtype, self.devices, rows=self.rows)
+        return self.inp(given, shape, name), given
+
+    def _dyn_out(self, tables):
+        dos = (_abi.DynOut * self.G)()
+        for name, table in tables.items():
+            for do, ptr in zip(dos, table):
+                setattr(do, name, ptr)
+        return dos
+
+
+def _marshaller(where, dtype, q):
+    """where a controller's call runs -> its marshaller.  where: a device ordinal; a list of device ordinals that one
+    host batch is cut over; or, when q is a ShardedArray, the streams of its shards (None: the library's own)"""
+    if isinstance(q, ShardedArray):
+        return _Cut(q, dtype, where)
+    return _HostBatch(dtype, where) if isinstance(where, list) else _Args(dtype, where)
+
+
+# ---------------------------------------------------------------------------- the four families with sharded forms
+# One binder each: the family's arrays, their row shapes and roles, stated once against whichever marshaller `m` the
+# call runs on.  The C entries of a family take the same arguments but for m.batch / m.where.
+def _entry(family, m):
+    return getattr(lib(), f"abrk_{family}_{m.form}")
+
+
+def _bind_osc(m, n, q, dq, target, target_velocity, integrated_error, u_null_ext, u, training_signal):
+    """-> (B, the eight array arguments of the abrk_osc_* entries, u or (u, training_signal))"""
+    B = q.shape[0]
+    joints, task = (B, n), (B, 6)
+    inp = m.inp
+    ptrs = [inp(q, joints, "q"), inp(dq, joints, "dq"), inp(target, task, "target"),
+            inp(target_velocity, task, "target_velocity"), m.inout(integrated_error, task, "integrated_error"),
+            inp(u_null_ext, joints, "u_null_ext"), None, None]
+    ptrs[6], uo = m.out(u, joints, "u")
+    ptrs[7], tso = m.opt_out(training_signal, joints, "training_signal")
+    return B, ptrs, uo if tso is None else (uo, tso)
+
+
+def _osc(m, arm_id, n, params, q, dq, target, target_velocity=None, integrated_error=None, u_null_ext=None, u=None,
+         training_signal=False):
+    B, ptrs, ret = _bind_osc(m, n, q, dq, target, target_velocity, integrated_error, u_null_ext, u, training_signal)
+    check(_entry("osc_generate", m)(arm_id, m.code, C.byref(params), m.batch(B), *ptrs, *m.where))
+    return ret
+
+
+def _bind_sliding(m, n, params, q, dq, target, target_velocity, target_acc, u, want_s):
+    """-> (B, the seven array arguments of the abrk_sliding_* entries, u or (u, s))"""
+    B = q.shape[0]
+    nt = 3 if params.cartesian else n
+    ptrs = [m.inp(q, (B, n), "q"), m.inp(dq, (B, n), "dq"), m.inp(target, (B, nt), "target"),
+            m.inp(target_velocity, (B, nt), "target_velocity"), m.inp(target_acc, (B, nt), "target_acc")]
+    up, uo = m.out(u, (B, n), "u")
+    sp, so = m.opt_out(want_s, (B, n), "s")
+    return B, ptrs + [up, sp], uo if so is None else (uo, so)
+
+
+def _sliding(m, arm_id, n, params, q, dq, target, target_velocity=None, target_acc=None, u=None, want_s=False):
+    B, ptrs, ret = _bind_sliding(m, n, params, q, dq, target, target_velocity, target_acc, u, want_s)
+    check(_entry("sliding_generate", m)(arm_id, m.code, C.byref(params), m.batch(B), *ptrs, *m.where))
+    return ret
+
+
+def _joint(m, arm_id, n, ctrl, account_for_gravity, q, dq, target=None, target_velocity=None, u=None):
+    B = q.shape[0]
+    ptrs = [m.inp(q, (B, n), "q"), m.inp(dq, (B, n), "dq"), m.inp(target, (B, n), "target"),
+            m.inp(target_velocity, (B, n), "target_velocity")]
+    up, uo = m.out(u, (B, n), "u")
+    check(_entry("joint_generate", m)(arm_id, m.code, C.byref(ctrl), int(bool(account_for_gravity)), m.batch(B), *ptrs, up,
+                                      *m.where))
+    return uo
+
+
+def _dynamics(m, arm_id, n, q, dq, frame, x_off, want, out=None):
+    B = q.shape[0]
+    frame = 2 * n + 1 if frame is None else frame
+    qp, dqp = m.inp(q, (B, n), "q"), m.inp(dq, (B, n), "dq")
+    bits, do, res = m.want(want, n, B, out)
+    xo = None if x_off is None else (C.c_double * 3)(*[float(v) for v in x_off])
+    check(_entry("dynamics", m)(arm_id, m.code, m.batch(B), qp, dqp, frame, xo, bits, do, *m.where))
+    return res
+
+
 def dynamics(arm_id, n, q, dq=None, frame=None, x_off=None, want=("M",), dtype=np.float64, device=0,
              stream=None, out=None):
     """robot_config.{Tx,J,M,g,C,dJ,R,T,T_inv,quaternion} for a batch (one launch, shared FK).
     Returns {name: array[B, ...]} for every name in `want`."""
-    a = _Args(dtype)
-    B = q.shape[0]
-    frame = 2 * n + 1 if frame is None else frame
-    qp = a.inp(q, (B, n), "q")
-    dqp = a.inp(dq, (B, n), "dq")
-    bits = 0
-    do = _abi.DynOut()
-    res = {}
-    for name in want:
-        bits |= _WANT_BITS[name]
-        ptr, obj = a.out(None if out is None else out.get(name), (B,) + _OUT_SHAPES[name](n), device, name)
-        setattr(do, name, ptr)
-        res[name] = obj
-    xo = None
-    if x_off is not None:
-        xo = (C.c_double * 3)(*[float(v) for v in x_off])
-    check(lib().abrk_dynamics_batch(arm_id, a.code, B, qp, dqp, frame, xo, bits, C.byref(do), device, _sp(stream)))
-    return res
+    return _dynamics(_Args(dtype, device, stream), arm_id, n, q, dq, frame, x_off, want, out)
 
 
 def osc_generate(arm_id, n, params, q, dq, target, target_velocity=None, integrated_error=None,
@@ -121,57 +322,27 @@ def osc_generate(arm_id, n, params, q, dq, target, target_velocity=None, integra
     want: subset of ("Tx", "J", "M", "g", "C", "dJ") -> the fused kernel (abrk_osc_generate_full_batch) also writes those
     robot_config outputs of the controller's ref_frame / xyz_offset; the return value gains a dict of them
     (`out`: optional dict of preallocated arrays)."""
-    a = _Args(dtype)
-    B = q.shape[0]
-    qp = a.inp(q, (B, n), "q")
-    dqp = a.inp(dq, (B, n), "dq")
-    tp = a.inp(target, (B, 6), "target")
-    tvp = a.inp(target_velocity, (B, 6), "target_velocity")
-    unp = a.inp(u_null_ext, (B, n), "u_null_ext")
-    iep = None
-    if integrated_error is not None:
-        if isinstance(integrated_error, DeviceArray):
-            iep = a.inp(integrated_error, (B, 6), "integrated_error")
-        else:
-            if (not isinstance(integrated_error, np.ndarray) or integrated_error.dtype != a.np_dtype
-                    or integrated_error.shape != (B, 6) or not integrated_error.flags.c_contiguous):
-                raise ValueError("integrated_error must be a C-contiguous ndarray [B,6] of the call dtype")
-            a._mode(False)
-            iep = integrated_error.ctypes.data
-    up, uo = a.out(u, (B, n), device, "u")
-    tsp, tso = None, None
-    if training_signal is not False and training_signal is not None:
-        tsp, tso = a.out(None if training_signal is True else training_signal, (B, n), device, "training_signal")
-    if want:
-        bits, do, res = 0, _abi.DynOut(), {}
-        for name in want:
-            if name not in ("Tx", "J", "M", "g", "C", "dJ"):
-                raise ValueError(f"the fused kernel offers Tx, J, M, g, C, dJ - not {name!r}")
-            bits |= _WANT_BITS[name]
-            ptr, obj = a.out(None if out is None else out.get(name), (B,) + _OUT_SHAPES[name](n), device, name)
-            setattr(do, name, ptr)
-            res[name] = obj
-        check(lib().abrk_osc_generate_full_batch(arm_id, a.code, C.byref(params), B, qp, dqp, tp, tvp, iep, unp, up,
-                                                 tsp, bits, C.byref(do), device, _sp(stream)))
-        return (uo, tso, res) if tso is not None else (uo, res)
-    check(lib().abrk_osc_generate_batch(arm_id, a.code, C.byref(params), B, qp, dqp, tp, tvp, iep, unp, up, tsp,
-                                        device, _sp(stream)))
-    return (uo, tso) if tso is not None else uo
+    m = _Args(dtype, device, stream)
+    B, ptrs, ret = _bind_osc(m, n, q, dq, target, target_velocity, integrated_error, u_null_ext, u, training_signal)
+    if not want:  # (the call a host-driven loop makes per tick: its entry is named here, not looked up as _osc does)
+        check(lib().abrk_osc_generate_batch(arm_id, m.code, C.byref(params), B, *ptrs, *m.where))
+        return ret
+    bits, do, res = m.want(want, n, B, out, ("Tx", "J", "M", "g", "C", "dJ"))
+    check(lib().abrk_osc_generate_full_batch(arm_id, m.code, C.byref(params), B, *ptrs, bits, do, *m.where))
+    return ret + (res,) if type(ret) is tuple else (ret, res)
 
 
 def osc_generate_coop(arm_id, n, params, q, dq, target, lanes_per_arm, u=None, training_signal=False, dtype=np.float64,
                       device=0, stream=None):
     """The wave-cooperative mapping of the plain OSC law (abrk_osc_generate_coop_batch; ur5, fp64): K = lanes_per_arm
     lanes per arm instance.  Measurement variant - see profiles/round2/coop_ab.md."""
-    a = _Args(dtype)
+    a = _Args(dtype, device)
     B = q.shape[0]
     qp = a.inp(q, (B, n), "q")
     dqp = a.inp(dq, (B, n), "dq")
     tp = a.inp(target, (B, 6), "target")
-    up, uo = a.out(u, (B, n), device, "u")
-    tsp, tso = None, None
-    if training_signal is not False and training_signal is not None:
-        tsp, tso = a.out(None if training_signal is True else training_signal, (B, n), device, "training_signal")
+    up, uo = a.out(u, (B, n), "u")
+    tsp, tso = a.opt_out(training_signal, (B, n), "training_signal")
     check(lib().abrk_osc_generate_coop_batch(arm_id, a.code, C.byref(params), B, qp, dqp, tp, up, tsp,
                                              int(lanes_per_arm), device, _sp(stream)))
     return (uo, tso) if tso is not None else uo
@@ -181,124 +352,26 @@ def osc_generate_sharded(arm_id, n, params, q, dq, target, devices, target_veloc
                          u_null_ext=None, u=None, training_signal=False, dtype=np.float64):
     """OSC.generate of ONE host batch over several devices (abrk_osc_generate_sharded): contiguous row shards, shard g
     on devices[g], no collective.  NumPy arrays only.  Returns u or (u, training_signal)."""
-    a = _Args(dtype)
-    B = q.shape[0]
-    for name, arr in (("q", q), ("dq", dq), ("target", target), ("target_velocity", target_velocity),
-                      ("u_null_ext", u_null_ext), ("u", u)):
-        if isinstance(arr, DeviceArray):
-            raise TypeError(f"{name}: the sharded call takes NumPy arrays (a DeviceArray lives on one device)")
-    qp = a.inp(q, (B, n), "q")
-    dqp = a.inp(dq, (B, n), "dq")
-    tp = a.inp(target, (B, 6), "target")
-    tvp = a.inp(target_velocity, (B, 6), "target_velocity")
-    unp = a.inp(u_null_ext, (B, n), "u_null_ext")
-    iep = None
-    if integrated_error is not None:
-        if (not isinstance(integrated_error, np.ndarray) or integrated_error.dtype != a.np_dtype
-                or integrated_error.shape != (B, 6) or not integrated_error.flags.c_contiguous):
-            raise ValueError("integrated_error must be a C-contiguous ndarray [B,6] of the call dtype")
-        iep = integrated_error.ctypes.data
-    up, uo = a.out(u, (B, n), 0, "u")
-    tsp, tso = None, None
-    if training_signal is not False and training_signal is not None:
-        tsp, tso = a.out(None if training_signal is True else training_signal, (B, n), 0, "training_signal")
-    devs = (C.c_int * len(devices))(*[int(d) for d in devices])
-    check(lib().abrk_osc_generate_sharded(arm_id, a.code, C.byref(params), B, qp, dqp, tp, tvp, iep, unp, up, tsp,
-                                          len(devices), devs))
-    return (uo, tso) if tso is not None else uo
-
-
-def _host_only(**arrays):
-    for name, arr in arrays.items():
-        if isinstance(arr, DeviceArray):
-            raise TypeError(f"{name}: the sharded calls take NumPy arrays (a DeviceArray lives on one device)")
+    return _osc(_HostBatch(dtype, devices), arm_id, n, params, q, dq, target, target_velocity, integrated_error,
+                u_null_ext, u, training_signal)
 
 
 def sliding_generate_sharded(arm_id, n, params, q, dq, target, devices, target_velocity=None, target_acc=None,
                              want_s=False, dtype=np.float64):
     """Sliding.generate of ONE host batch over several devices (abrk_sliding_generate_sharded)"""
-    _host_only(q=q, dq=dq, target=target, target_velocity=target_velocity, target_acc=target_acc)
-    a = _Args(dtype)
-    B = q.shape[0]
-    nt = 3 if params.cartesian else n
-    qp, dqp = a.inp(q, (B, n), "q"), a.inp(dq, (B, n), "dq")
-    tp = a.inp(target, (B, nt), "target")
-    tvp, tap = a.inp(target_velocity, (B, nt), "target_velocity"), a.inp(target_acc, (B, nt), "target_acc")
-    up, uo = a.out(None, (B, n), 0, "u")
-    sp, so = a.out(None, (B, n), 0, "s") if want_s else (None, None)
-    devs = (C.c_int * len(devices))(*[int(d) for d in devices])
-    check(lib().abrk_sliding_generate_sharded(arm_id, a.code, C.byref(params), B, qp, dqp, tp, tvp, tap, up, sp,
-                                              len(devices), devs))
-    return (uo, so) if want_s else uo
+    return _sliding(_HostBatch(dtype, devices), arm_id, n, params, q, dq, target, target_velocity, target_acc, None,
+                    bool(want_s))
 
 
 def joint_generate_sharded(arm_id, n, ctrl, account_for_gravity, q, dq, devices, target=None, target_velocity=None,
                            dtype=np.float64):
     """Joint / Damping / RestingConfig.generate of ONE host batch over several devices (abrk_joint_generate_sharded)"""
-    _host_only(q=q, dq=dq, target=target, target_velocity=target_velocity)
-    a = _Args(dtype)
-    B = q.shape[0]
-    qp, dqp = a.inp(q, (B, n), "q"), a.inp(dq, (B, n), "dq")
-    tp, tvp = a.inp(target, (B, n), "target"), a.inp(target_velocity, (B, n), "target_velocity")
-    up, uo = a.out(None, (B, n), 0, "u")
-    devs = (C.c_int * len(devices))(*[int(d) for d in devices])
-    check(lib().abrk_joint_generate_sharded(arm_id, a.code, C.byref(ctrl), int(bool(account_for_gravity)), B, qp, dqp, tp,
-                                            tvp, up, len(devices), devs))
-    return uo
+    return _joint(_HostBatch(dtype, devices), arm_id, n, ctrl, account_for_gravity, q, dq, target, target_velocity)
 
 
 def dynamics_sharded(arm_id, n, q, devices, dq=None, frame=None, x_off=None, want=("M",), dtype=np.float64):
     """robot_config.{Tx,J,M,g,C,dJ,R,T,T_inv,quaternion} of ONE host batch over several devices (abrk_dynamics_sharded)"""
-    _host_only(q=q, dq=dq)
-    a = _Args(dtype)
-    B = q.shape[0]
-    frame = 2 * n + 1 if frame is None else frame
-    qp, dqp = a.inp(q, (B, n), "q"), a.inp(dq, (B, n), "dq")
-    bits, do, res = 0, _abi.DynOut(), {}
-    for name in want:
-        bits |= _WANT_BITS[name]
-        ptr, obj = a.out(None, (B,) + _OUT_SHAPES[name](n), 0, name)
-        setattr(do, name, ptr)
-        res[name] = obj
-    xo = None if x_off is None else (C.c_double * 3)(*[float(v) for v in x_off])
-    devs = (C.c_int * len(devices))(*[int(d) for d in devices])
-    check(lib().abrk_dynamics_sharded(arm_id, a.code, B, qp, dqp, frame, xo, bits, C.byref(do), len(devices), devs))
-    return res
-
-
-# ---------------------------------------------------------------------------- resident shards (SURVEY 8e)
-class _Cut:
-    """abrk_shard_cut + the pointer tables of one resident call (sharding.ShardedArray arguments)"""
-
-    def __init__(self, like, dtype, streams=None):
-        self.devices, self.rows = list(like.devices), list(like.rows)
-        self.G = len(self.devices)
-        self.np_dtype, self.code = np.dtype(dtype), _dtype_code(dtype)
-        self._dev = (C.c_int32 * self.G)(*self.devices)
-        self._rows = (C.c_int64 * self.G)(*self.rows)
-        self._streams = None
-        if streams is not None:
-            if len(streams) != self.G:
-                raise ValueError(f"{len(streams)} streams for {self.G} shards")
-            self._streams = (C.c_void_p * self.G)(*[_sp(st) for st in streams])
-        self.c = _abi.ShardCut(self.G, self._dev, self._rows, self._streams)
-
-    def tab(self, arr, tail, name):
-        """pointer table of a ShardedArray (None -> NULL), checked against the cut"""
-        if arr is None:
-            return None
-        if list(arr.devices) != self.devices or list(arr.rows) != self.rows:
-            raise ValueError(f"{name}: cut over other devices / rows than q")
-        if arr.dtype != self.np_dtype or tuple(arr.shape[1:]) != tuple(tail):
-            raise ValueError(f"{name}: expected {self.np_dtype}[B{tuple(tail)}], got {arr.dtype}{arr.shape}")
-        return (C.c_void_p * self.G)(*[p.ptr for p in arr.parts])
-
-    def out(self, given, tail, name):
-        from .sharding import ShardedArray
-
-        if given is None:
-            given = ShardedArray.empty((sum(self.rows),) + tuple(tail), self.np_dtype, self.devices, rows=self.rows)
-        return self.tab(given, tail, name), given
+    return _dynamics(_HostBatch(dtype, devices), arm_id, n, q, dq, frame, x_off, want)
 
 
 def osc_generate_resident(arm_id, n, params, q, dq, target, target_velocity=None, integrated_error=None,
@@ -307,62 +380,27 @@ def osc_generate_resident(arm_id, n, params, q, dq, target, target_velocity=None
     sharding.ShardedArray cut the same way; the call only enqueues (shard g on streams[g], or on the library's own
     stream of its (device, slot)).  integrated_error [B,6] stays with its shards.  Returns u, or (u, training_signal),
     as ShardedArrays - not yet complete: sync with `shards_sync(u)` / MultiDevice.sync()."""
-    c = _Cut(q, dtype, streams)
-    qp, dqp, tp = c.tab(q, (n,), "q"), c.tab(dq, (n,), "dq"), c.tab(target, (6,), "target")
-    tvp, unp = c.tab(target_velocity, (6,), "target_velocity"), c.tab(u_null_ext, (n,), "u_null_ext")
-    iep = c.tab(integrated_error, (6,), "integrated_error")
-    up, uo = c.out(u, (n,), "u")
-    tsp, tso = None, None
-    if training_signal is not False and training_signal is not None:
-        tsp, tso = c.out(None if training_signal is True else training_signal, (n,), "training_signal")
-    check(lib().abrk_osc_generate_resident(arm_id, c.code, C.byref(params), C.byref(c.c), qp, dqp, tp, tvp, iep, unp, up,
-                                           tsp))
-    return (uo, tso) if tso is not None else uo
+    return _osc(_Cut(q, dtype, streams), arm_id, n, params, q, dq, target, target_velocity, integrated_error, u_null_ext,
+                u, training_signal)
 
 
 def sliding_generate_resident(arm_id, n, params, q, dq, target, target_velocity=None, target_acc=None, u=None,
                               want_s=False, dtype=np.float64, streams=None):
     """Sliding.generate on resident shards (abrk_sliding_generate_resident)"""
-    c = _Cut(q, dtype, streams)
-    nt = 3 if params.cartesian else n
-    qp, dqp, tp = c.tab(q, (n,), "q"), c.tab(dq, (n,), "dq"), c.tab(target, (nt,), "target")
-    tvp, tap = c.tab(target_velocity, (nt,), "target_velocity"), c.tab(target_acc, (nt,), "target_acc")
-    up, uo = c.out(u, (n,), "u")
-    sp, so = c.out(None if want_s is True else want_s, (n,), "s") if want_s else (None, None)
-    check(lib().abrk_sliding_generate_resident(arm_id, c.code, C.byref(params), C.byref(c.c), qp, dqp, tp, tvp, tap, up, sp))
-    return (uo, so) if want_s else uo
+    return _sliding(_Cut(q, dtype, streams), arm_id, n, params, q, dq, target, target_velocity, target_acc, u, want_s)
 
 
 def joint_generate_resident(arm_id, n, ctrl, account_for_gravity, q, dq, target=None, target_velocity=None, u=None,
                             dtype=np.float64, streams=None):
     """Joint / Damping / RestingConfig.generate on resident shards (abrk_joint_generate_resident)"""
-    c = _Cut(q, dtype, streams)
-    qp, dqp = c.tab(q, (n,), "q"), c.tab(dq, (n,), "dq")
-    tp, tvp = c.tab(target, (n,), "target"), c.tab(target_velocity, (n,), "target_velocity")
-    up, uo = c.out(u, (n,), "u")
-    check(lib().abrk_joint_generate_resident(arm_id, c.code, C.byref(ctrl), int(bool(account_for_gravity)), C.byref(c.c),
-                                             qp, dqp, tp, tvp, up))
-    return uo
+    return _joint(_Cut(q, dtype, streams), arm_id, n, ctrl, account_for_gravity, q, dq, target, target_velocity, u)
 
 
 def dynamics_resident(arm_id, n, q, dq=None, frame=None, x_off=None, want=("M",), dtype=np.float64, streams=None,
                       out=None):
     """robot_config.{Tx,J,M,g,C,dJ,R,T,T_inv,quaternion} on resident shards (abrk_dynamics_resident):
     {name: ShardedArray}"""
-    c = _Cut(q, dtype, streams)
-    frame = 2 * n + 1 if frame is None else frame
-    qp, dqp = c.tab(q, (n,), "q"), c.tab(dq, (n,), "dq")
-    bits, res = 0, {}
-    dos = (_abi.DynOut * c.G)()
-    for name in want:
-        bits |= _WANT_BITS[name]
-        _, obj = c.out(None if out is None else out.get(name), _OUT_SHAPES[name](n), name)
-        for g in range(c.G):
-            setattr(dos[g], name, obj.parts[g].ptr)
-        res[name] = obj
-    xo = None if x_off is None else (C.c_double * 3)(*[float(v) for v in x_off])
-    check(lib().abrk_dynamics_resident(arm_id, c.code, C.byref(c.c), qp, dqp, frame, xo, bits, dos))
-    return res
+    return _dynamics(_Cut(q, dtype, streams), arm_id, n, q, dq, frame, x_off, want, out)
 
 
 def shards_sync(like, streams=None):
@@ -382,7 +420,7 @@ def osc_law(n, params, J, M, dq, target, g=None, Cdq=None, xyz=None, R=None, q=N
             integrated_error=None, u_null_ext=None, training_signal=False, dtype=np.float64, device=0, stream=None):
     """The OSC control law on caller-supplied dynamics (abrk_osc_law_batch): J [B,6,n], M [B,n,n] and,
     as the controller options require, g [B,n], Cdq [B,n], xyz [B,3], R [B,3,3], q [B,n]."""
-    a = _Args(dtype)
+    a = _Args(dtype, device)
     B = J.shape[0]
     Jp = a.inp(J, (B, 6, n), "J")
     Mp = a.inp(M, (B, n, n), "M")
@@ -395,53 +433,43 @@ def osc_law(n, params, J, M, dq, target, g=None, Cdq=None, xyz=None, R=None, q=N
     tp = a.inp(target, (B, 6), "target")
     tvp = a.inp(target_velocity, (B, 6), "target_velocity")
     unp = a.inp(u_null_ext, (B, n), "u_null_ext")
-    iep = None
-    if integrated_error is not None:
-        if isinstance(integrated_error, DeviceArray):
-            iep = a.inp(integrated_error, (B, 6), "integrated_error")
-        else:
-            if (not isinstance(integrated_error, np.ndarray) or integrated_error.dtype != a.np_dtype
-                    or integrated_error.shape != (B, 6) or not integrated_error.flags.c_contiguous):
-                raise ValueError("integrated_error must be a C-contiguous ndarray [B,6] of the call dtype")
-            iep = integrated_error.ctypes.data
-    up, uo = a.out(None, (B, n), device, "u")
-    tsp, tso = (None, None)
-    if training_signal:
-        tsp, tso = a.out(None, (B, n), device, "training_signal")
+    iep = a.inout(integrated_error, (B, 6), "integrated_error")
+    up, uo = a.out(None, (B, n), "u")
+    tsp, tso = a.opt_out(bool(training_signal), (B, n), "training_signal")
     check(lib().abrk_osc_law_batch(n, a.code, C.byref(params), B, Jp, Mp, gp, cp, xp, Rp, qp, dqp, tp, tvp, iep, unp,
                                    up, tsp, device, _sp(stream)))
-    return (uo, tso) if training_signal else uo
+    return (uo, tso) if tso is not None else uo
 
 
 def osc_mx(n, M, J, threshold=1e-3, want_minv=True, dtype=np.float64, device=0, stream=None):
     """OSC._Mx (osc.py:120-147) for B rows: M [B,n,n], J [B,k,n] -> (Mx [B,k,k], M_inv [B,n,n] or None)"""
-    a = _Args(dtype)
+    a = _Args(dtype, device)
     B, k = J.shape[0], J.shape[1]
     Mp = a.inp(M, (B, n, n), "M")
     Jp = a.inp(J, (B, k, n), "J")
-    xp, xo = a.out(None, (B, k, k), device, "Mx")
-    ip, io = a.out(None, (B, n, n), device, "M_inv") if want_minv else (None, None)
+    xp, xo = a.out(None, (B, k, k), "Mx")
+    ip, io = a.out(None, (B, n, n), "M_inv") if want_minv else (None, None)
     check(lib().abrk_osc_mx_batch(n, k, a.code, B, Mp, Jp, float(threshold), xp, ip, device, _sp(stream)))
     return xo, io
 
 
 def osc_velocity_limiting(params, u_task, dtype=np.float64, device=0, stream=None):
     """OSC._velocity_limiting (osc.py:198-215) for B rows of u_task [B,6]"""
-    a = _Args(dtype)
+    a = _Args(dtype, device)
     B = u_task.shape[0]
     ip = a.inp(u_task, (B, 6), "u_task")
-    op, oo = a.out(None, (B, 6), device, "out")
+    op, oo = a.out(None, (B, 6), "out")
     check(lib().abrk_osc_velocity_limiting_batch(a.code, C.byref(params), B, ip, op, device, _sp(stream)))
     return oo
 
 
 def osc_orientation_forces(algorithm, R, target_abg, dtype=np.float64, device=0, stream=None):
     """OSC._calc_orientation_forces (osc.py:149-196) from R [B,3,3] = robot_config.R(ref_frame, q), target_abg [B,3]"""
-    a = _Args(dtype)
+    a = _Args(dtype, device)
     B = R.shape[0]
     Rp = a.inp(R, (B, 3, 3), "R")
     tp = a.inp(target_abg, (B, 3), "target_abg")
-    op, oo = a.out(None, (B, 3), device, "u_task_orientation")
+    op, oo = a.out(None, (B, 3), "u_task_orientation")
     check(lib().abrk_osc_orientation_forces_batch(int(algorithm), a.code, B, Rp, tp, op, device, _sp(stream)))
     return oo
 
@@ -453,54 +481,32 @@ _TF_WIDTHS = {0: (3, 0, 4), 1: (3, 0, 4), 2: (9, 0, 4), 3: (4, 4, 4), 4: (4, 0, 
 def transformations(op, a, b=None, dtype=np.float64, device=0, stream=None):
     """abrk_transformations_batch: op = ABRK_TF_* (include/abrk.h); a [B,wa], b [B,wb] or None -> out [B,wo]"""
     wa, wb, wo = _TF_WIDTHS[int(op)]
-    ar = _Args(dtype)
+    ar = _Args(dtype, device)
     B = a.shape[0]
     ap = ar.inp(a, (B, wa), "a")
     bp = ar.inp(b, (B, wb), "b") if wb else None
-    op_, oo = ar.out(None, (B, wo), device, "out")
+    op_, oo = ar.out(None, (B, wo), "out")
     check(lib().abrk_transformations_batch(int(op), ar.code, B, ap, bp, op_, device, _sp(stream)))
     return oo
 
 
 def sliding_generate(arm_id, n, params, q, dq, target, target_velocity=None, target_acc=None, u=None,
                      want_s=False, dtype=np.float64, device=0, stream=None):
-    a = _Args(dtype)
-    B = q.shape[0]
-    nt = 3 if params.cartesian else n
-    qp = a.inp(q, (B, n), "q")
-    dqp = a.inp(dq, (B, n), "dq")
-    tp = a.inp(target, (B, nt), "target")
-    tvp = a.inp(target_velocity, (B, nt), "target_velocity")
-    tap = a.inp(target_acc, (B, nt), "target_acc")
-    up, uo = a.out(u, (B, n), device, "u")
-    sp, so = (None, None)
-    if want_s:
-        sp, so = a.out(None, (B, n), device, "s")
-    check(lib().abrk_sliding_generate_batch(arm_id, a.code, C.byref(params), B, qp, dqp, tp, tvp, tap, up, sp,
-                                            device, _sp(stream)))
-    return (uo, so) if want_s else uo
+    return _sliding(_Args(dtype, device, stream), arm_id, n, params, q, dq, target, target_velocity, target_acc, u,
+                    bool(want_s))
 
 
 def joint_generate(arm_id, n, ctrl, account_for_gravity, q, dq, target=None, target_velocity=None, u=None,
                    dtype=np.float64, device=0, stream=None):
-    a = _Args(dtype)
-    B = q.shape[0]
-    qp = a.inp(q, (B, n), "q")
-    dqp = a.inp(dq, (B, n), "dq")
-    tp = a.inp(target, (B, n), "target")
-    tvp = a.inp(target_velocity, (B, n), "target_velocity")
-    up, uo = a.out(u, (B, n), device, "u")
-    check(lib().abrk_joint_generate_batch(arm_id, a.code, C.byref(ctrl), int(bool(account_for_gravity)), B, qp, dqp,
-                                          tp, tvp, up, device, _sp(stream)))
-    return uo
+    return _joint(_Args(dtype, device, stream), arm_id, n, ctrl, account_for_gravity, q, dq, target, target_velocity, u)
 
 
 def avoid_joint_limits_generate(n, params, q, u=None, accumulate=False, dtype=np.float64, device=0, stream=None):
     """AvoidJointLimits.generate for B states; accumulate: u += signal (u must then be given)."""
-    a = _Args(dtype)
+    a = _Args(dtype, device)
     B = q.shape[0]
     qp = a.inp(q, (B, n), "q")
-    up, uo = a.out(u, (B, n), device, "u")
+    up, uo = a.out(u, (B, n), "u")
     check(lib().abrk_avoid_joint_limits_generate_batch(n, a.code, C.byref(params), B, qp, up,
                                                        int(bool(accumulate and u is not None)), device, _sp(stream)))
     return uo
@@ -509,11 +515,11 @@ def avoid_joint_limits_generate(n, params, q, u=None, accumulate=False, dtype=np
 def floating_generate(arm_id, n, dynamic, task_space, q, dq=None, u=None, accumulate=False, dtype=np.float64,
                       device=0, stream=None):
     """Floating.generate for B states."""
-    a = _Args(dtype)
+    a = _Args(dtype, device)
     B = q.shape[0]
     qp = a.inp(q, (B, n), "q")
     dqp = a.inp(dq, (B, n), "dq") if dynamic else None
-    up, uo = a.out(u, (B, n), device, "u")
+    up, uo = a.out(u, (B, n), "u")
     check(lib().abrk_floating_generate_batch(arm_id, a.code, int(bool(dynamic)), int(bool(task_space)), B, qp, dqp,
                                              up, int(bool(accumulate and u is not None)), device, _sp(stream)))
     return uo
@@ -522,31 +528,20 @@ def floating_generate(arm_id, n, dynamic, task_space, q, dq=None, u=None, accumu
 def avoid_obstacles_generate(arm_id, n, params, q, u=None, accumulate=False, dtype=np.float64, device=0,
                              stream=None):
     """AvoidObstacles.generate for B states (obstacles shared by all rows)."""
-    a = _Args(dtype)
+    a = _Args(dtype, device)
     B = q.shape[0]
     qp = a.inp(q, (B, n), "q")
-    up, uo = a.out(u, (B, n), device, "u")
+    up, uo = a.out(u, (B, n), "u")
     check(lib().abrk_avoid_obstacles_generate_batch(arm_id, a.code, C.byref(params), B, qp, up,
                                                     int(bool(accumulate and u is not None)), device, _sp(stream)))
     return uo
 
 
-def _inout(a, arr, shape, name):
-    """in/out state array: DeviceArray, or a C-contiguous ndarray of the call dtype updated in place"""
-    if isinstance(arr, DeviceArray):
-        return a.inp(arr, shape, name)
-    if (not isinstance(arr, np.ndarray) or arr.dtype != a.np_dtype or arr.shape != tuple(shape)
-            or not arr.flags.c_contiguous):
-        raise ValueError(f"{name} must be a C-contiguous ndarray {tuple(shape)} of the call dtype (updated in place)")
-    a._mode(False)
-    return arr.ctypes.data
-
-
 def twolink_step(plant, q, dq, u, dtype=np.float64, device=0, stream=None):
     """ArmSim._step for a batch: (q, dq) [B,2] advanced in place by torques u [B,2]."""
-    a = _Args(dtype)
+    a = _Args(dtype, device)
     B = q.shape[0]
-    qp, dqp = _inout(a, q, (B, 2), "q"), _inout(a, dq, (B, 2), "dq")
+    qp, dqp = a.inout(q, (B, 2), "q"), a.inout(dq, (B, 2), "dq")
     up = a.inp(u, (B, 2), "u")
     check(lib().abrk_twolink_step_batch(a.code, C.byref(plant), B, qp, dqp, up, device, _sp(stream)))
 
@@ -556,15 +551,15 @@ def forward_dynamics(arm_id, n, q, dq, u, ddq=None, dtype=np.float64, device=0, 
     """ddq = M(q)^-1 (tau - C(q,dq) dq - g(q)) for B states: q, dq, u [B,n] -> ddq [B,n].  tau = u, or with `effects`
     (_abi.make_plant_effects), `tau_ext` [B,n], `wrench` [B,6]: the saturated u plus the loads and the friction
     (include/abrk.h, abrk_plant_effects).  With all three None this is the plain entry point."""
-    a = _Args(dtype)
+    a = _Args(dtype, device)
     B = q.shape[0]
     qp, dqp, up = a.inp(q, (B, n), "q"), a.inp(dq, (B, n), "dq"), a.inp(u, (B, n), "u")
     if effects is None and tau_ext is None and wrench is None:
-        op, oo = a.out(ddq, (B, n), device, "ddq")
+        op, oo = a.out(ddq, (B, n), "ddq")
         check(lib().abrk_forward_dynamics_batch(arm_id, a.code, B, qp, dqp, up, op, device, _sp(stream)))
         return oo
     ep, wp = a.inp(tau_ext, (B, n), "tau_ext"), a.inp(wrench, (B, 6), "wrench")
-    op, oo = a.out(ddq, (B, n), device, "ddq")
+    op, oo = a.out(ddq, (B, n), "ddq")
     check(lib().abrk_forward_dynamics_fx_batch(arm_id, a.code, None if effects is None else C.byref(effects), B, qp,
                                                dqp, up, ep, wp, op, device, _sp(stream)))
     return oo
@@ -577,9 +572,9 @@ def plant_step(arm_id, n, params, q, dq, u, dtype=np.float64, device=0, stream=N
     joint-space disturbance) and `wrench` [B,6] (a world-frame wrench at the end effector) make the plant non-ideal
     (include/abrk.h, abrk_plant_effects); with all three None this is the plain entry point.  Recorded into a plan, the
     contents of tau_ext and wrench are read at every replay."""
-    a = _Args(dtype)
+    a = _Args(dtype, device)
     B = q.shape[0]
-    qp, dqp = _inout(a, q, (B, n), "q"), _inout(a, dq, (B, n), "dq")
+    qp, dqp = a.inout(q, (B, n), "q"), a.inout(dq, (B, n), "dq")
     up = a.inp(u, (B, n), "u")
     if effects is None and tau_ext is None and wrench is None:
         check(lib().abrk_plant_step_batch(arm_id, a.code, C.byref(params), B, qp, dqp, up, device, _sp(stream)))
@@ -593,29 +588,20 @@ def osc_rollout_twolink(arm_id, params, plant, q, dq, target, n_steps, every=0, 
                         want_traj=False, dtype=np.float64, device=0, stream=None):
     """n_steps x { OSC.generate ; ArmSim._step } in one launch.  q, dq [B,2] are advanced in place.
     Returns (q_traj, dq_traj, u_traj) [B, n_steps // every, 2] when want_traj, else None."""
-    a = _Args(dtype)
+    a = _Args(dtype, device)
     B = q.shape[0]
-    qp, dqp = _inout(a, q, (B, 2), "q"), _inout(a, dq, (B, 2), "dq")
+    qp, dqp = a.inout(q, (B, 2), "q"), a.inout(dq, (B, 2), "dq")
     tp = a.inp(target, (B, 6), "target")
-    iep = None if integrated_error is None else _inout(a, integrated_error, (B, 6), "integrated_error")
+    iep = a.inout(integrated_error, (B, 6), "integrated_error")
     outs, ptrs = (None, None, None), (None, None, None)
     if want_traj:
         n_chk = n_steps // every if every else 0
-        pairs = [a.out(None, (B, n_chk, 2), device, nm) for nm in ("q_traj", "dq_traj", "u_traj")]
+        pairs = [a.out(None, (B, n_chk, 2), nm) for nm in ("q_traj", "dq_traj", "u_traj")]
         ptrs, outs = tuple(p for p, _ in pairs), tuple(o for _, o in pairs)
     check(lib().abrk_osc_rollout_twolink_batch(arm_id, a.code, C.byref(params), C.byref(plant), B, int(n_steps),
                                                int(every), qp, dqp, tp, iep, ptrs[0], ptrs[1], ptrs[2], device,
                                                _sp(stream)))
     return outs if want_traj else None
-
-
-def _i32(arr, shape, name, device_mode):
-    """an int32 array argument of the path entries: DeviceArray or C-contiguous ndarray, passed as it is"""
-    if isinstance(arr, DeviceArray) != device_mode:
-        raise TypeError("mixing DeviceArray and NumPy arguments in one call is not supported")
-    if arr.dtype != np.int32 or tuple(arr.shape) != tuple(shape) or (not device_mode and not arr.flags.c_contiguous):
-        raise ValueError(f"{name}: expected a C-contiguous int32 array {tuple(shape)}, got {arr.dtype}{tuple(arr.shape)}")
-    return arr.ptr if device_mode else arr.ctypes.data
 
 
 def _path_table(a, params, table, offsets):
@@ -639,7 +625,7 @@ def path_plan(params, table, offsets, start, target, device=0, stream=None):
     (n_timesteps [B] int32, rowplan [B,2] int32, dist_steps [B, n_samples]).  params: _abi.PathParams; table / offsets:
     the packed profile tables (controllers/path_planners/path_planner.py builds them).  Raises PathError (a ValueError)
     when a row has no path."""
-    a = _Args(np.float64)
+    a = _Args(np.float64, device)
     B = start.shape[0]
     sp, tp = a.inp(start, (B, 3), "start"), a.inp(target, (B, 3), "target")
     tabp, offp = _path_table(a, params, table, offsets)
@@ -649,7 +635,7 @@ def path_plan(params, table, offsets, start, target, device=0, stream=None):
     else:
         nt, rp = np.zeros((B,), np.int32), np.zeros((B, 2), np.int32)
         ntp, rpp = nt.ctypes.data, rp.ctypes.data
-    dsp, ds = a.out(None, (B, int(params.n_samples)), device, "dist_steps")
+    dsp, ds = a.out(None, (B, int(params.n_samples)), "dist_steps")
     check(lib().abrk_path_plan_batch(C.byref(params), tabp, offp, B, sp, tp, ntp, rpp, dsp, device, _sp(stream)))
     return nt, rp, ds
 
@@ -659,14 +645,14 @@ def path_fill(params, table, offsets, t_max, start, target, n_timesteps, rowplan
     """The fill and gradient passes (abrk_path_fill_batch) -> path [B, t_max, params.width]: row b is its path in
     [:n_timesteps[b]] and its last point after that.  A row with n_timesteps[b] == 0 or n_timesteps[b] > t_max is left
     as it was in every column: a path is never truncated."""
-    a = _Args(np.float64)
+    a = _Args(np.float64, device)
     B = start.shape[0]
     sp, tp = a.inp(start, (B, 3), "start"), a.inp(target, (B, 3), "target")
     sop, top = a.inp(start_orientation, (B, 3), "start_orientation"), a.inp(target_orientation, (B, 3), "target_orientation")
     dsp = a.inp(dist_steps, (B, int(params.n_samples)), "dist_steps")
-    ntp, rpp = _i32(n_timesteps, (B,), "n_timesteps", a.on_device), _i32(rowplan, (B, 2), "rowplan", a.on_device)
+    ntp, rpp = a.side(n_timesteps, (B,), "n_timesteps"), a.side(rowplan, (B, 2), "rowplan")
     tabp, offp = _path_table(a, params, table, offsets)
-    pp, po = a.out(path, (B, int(t_max), int(params.width)), device, "path")
+    pp, po = a.out(path, (B, int(t_max), int(params.width)), "path")
     check(lib().abrk_path_fill_batch(C.byref(params), tabp, offp, B, int(t_max), sp, tp, sop, top, ntp, rpp, dsp, pp,
                                      device, _sp(stream)))
     return po
@@ -677,16 +663,16 @@ def path_next(path, n_timesteps, counter, target, target_velocity=None, dtype=np
     path[b, counter[b], (0:3, 6:9)], target_velocity[b] = path[b, counter[b], (3:6, 9:12)], counter[b] advanced and
     clamped to n_timesteps[b] - 1.  path: float64 [B, Tmax, 6 | 12]; target / target_velocity: [B,6] of `dtype`, updated in
     place (a 6-wide path leaves their orientation columns alone); counter, n_timesteps: int32 [B]."""
-    a = _Args(dtype)
+    a = _Args(dtype, device)
     B, t_max, width = path.shape
     dev = isinstance(path, DeviceArray)
-    a._mode(dev)
+    a._mode(dev, "path")
     if path.dtype != np.float64 or (not dev and not path.flags.c_contiguous):
         raise ValueError("path: expected a C-contiguous float64 array [B, Tmax, W]")
     pp = path.ptr if dev else path.ctypes.data
-    ntp, cp = _i32(n_timesteps, (B,), "n_timesteps", dev), _i32(counter, (B,), "counter", dev)
-    tgp = _inout(a, target, (B, 6), "target")
-    tvp = None if target_velocity is None else _inout(a, target_velocity, (B, 6), "target_velocity")
+    ntp, cp = a.side(n_timesteps, (B,), "n_timesteps"), a.side(counter, (B,), "counter")
+    tgp = a.inout(target, (B, 6), "target")
+    tvp = a.inout(target_velocity, (B, 6), "target_velocity")
     check(lib().abrk_path_next_batch(a.code, B, int(t_max), int(width), pp, ntp, cp, tgp, tvp, device, _sp(stream)))
 
 
@@ -698,28 +684,22 @@ def loop_trace(arm_id, n, params, q, dq, u, target, counter, history=None, stats
     err_sumsq) and settle[b] are updated; counter[b] = t + 1.  params: _abi.make_trace_params.  q, dq, u [B,n], target [B,6]
     of `dtype` (None where no selected output needs one); counter, settle: int32 [B]; history: [capacity, B, W] of `dtype`;
     stats: float64 [B,4].  counter, history, stats and settle are updated in place."""
-    a = _Args(dtype)
+    a = _Args(dtype, device)
     src = next((x for x in (q, target, dq, u) if x is not None), None)
     if src is None:
         raise ValueError("loop_trace needs at least one of q, dq, u, target")
     B = src.shape[0]
-    dev = isinstance(src, DeviceArray)
     qp, dqp, up = a.inp(q, (B, n), "q"), a.inp(dq, (B, n), "dq"), a.inp(u, (B, n), "u")
     tp = a.inp(target, (B, 6), "target")
-    a._mode(dev)
-    cp = _i32(counter, (B,), "counter", dev)
+    cp = a.side(counter, (B,), "counter")
     hp = sp = sep = None
     if history is not None:
         W = _abi.trace_layout(int(params.columns), n)[1]
-        hp = _inout(a, history, (int(params.capacity), B, W), "history")
+        hp = a.inout(history, (int(params.capacity), B, W), "history")
     if stats is not None:
-        if isinstance(stats, DeviceArray) != dev:
-            raise TypeError("mixing DeviceArray and NumPy arguments in one call is not supported")
-        if stats.dtype != np.float64 or tuple(stats.shape) != (B, 4) or (not dev and not stats.flags.c_contiguous):
-            raise ValueError(f"stats: expected a C-contiguous float64 array {(B, 4)}, got {stats.dtype}{tuple(stats.shape)}")
-        sp = stats.ptr if dev else stats.ctypes.data
+        sp = a.side(stats, (B, 4), "stats", np.float64)
     if settle is not None:
-        sep = _i32(settle, (B,), "settle", dev)
+        sep = a.side(settle, (B,), "settle")
     check(lib().abrk_loop_trace_batch(arm_id, a.code, C.byref(params), B, qp, dqp, up, tp, cp, hp, sp, sep, device,
                                       _sp(stream)))
 
@@ -740,7 +720,7 @@ def adapt_step(params, enc, gain, bias, shift, scale, in0, training, state, in1=
     ([B,w0], [B,w1] with w0 + w1 = D: q and dq of a loop); training [B,O].  state: a dict of the seven arrays of
     adapt_state_shapes (v and ref may be missing for "lif_rate"), updated in place.  -> out [B,O], the filtered output;
     u_add [B,O], when given, has it added.  All arrays are of `dtype`, NumPy or DeviceArray alike."""
-    a = _Args(dtype)
+    a = _Args(dtype, device)
     D, O, N = int(params.n_input), int(params.n_output), int(params.n_neurons_total)
     B = in0.shape[0]
     w0 = in0.shape[1]
@@ -753,9 +733,9 @@ def adapt_step(params, enc, gain, bias, shift, scale, in0, training, state, in1=
     for name, shape in adapt_state_shapes(params, B).items():
         arr = state.get(name)
         if arr is not None:
-            setattr(st, name, _inout(a, arr, shape, name))
-    up = None if u_add is None else _inout(a, u_add, (B, O), "u_add")
-    op, oo = a.out(out, (B, O), device, "out")
+            setattr(st, name, a.inout(arr, shape, name))
+    up = a.inout(u_add, (B, O), "u_add")
+    op, oo = a.out(out, (B, O), "out")
     check(lib().abrk_adapt_step_batch(a.code, C.byref(params), B, *tabs, i0p, w0, i1p, w1, tp, C.byref(st), op, up,
                                       device, _sp(stream)))
     return oo
@@ -829,20 +809,10 @@ class OscPlan(Plan):
     def __init__(self, arm_id, n, params, q, dq, target, u, target_velocity=None, integrated_error=None,
                  u_null_ext=None, training_signal=None, dtype=np.float64, device=0, stream=None):
         Plan.__init__(self, device, stream)
-        a = _Args(dtype)
-        B = q.shape[0]
-        arrs = dict(q=(q, (B, n)), dq=(dq, (B, n)), target=(target, (B, 6)), target_velocity=(target_velocity, (B, 6)),
-                    integrated_error=(integrated_error, (B, 6)), u_null_ext=(u_null_ext, (B, n)), u=(u, (B, n)),
-                    training_signal=(training_signal, (B, n)))
-        ptr = {}
-        for name, (arr, shape) in arrs.items():
-            if arr is not None and not isinstance(arr, DeviceArray):
-                raise TypeError(f"{name}: launch plans take DeviceArrays")
-            ptr[name] = a.inp(arr, shape, name)
-        self._keep += [v[0] for v in arrs.values()] + [params]
-        self.id = check(lib().abrk_osc_plan_create(
-            arm_id, a.code, C.byref(params), B, ptr["q"], ptr["dq"], ptr["target"], ptr["target_velocity"],
-            ptr["integrated_error"], ptr["u_null_ext"], ptr["u"], ptr["training_signal"], device, _sp(stream)))
+        m = _PlanArgs(dtype, device, stream)
+        B, ptrs, _ = _bind_osc(m, n, q, dq, target, target_velocity, integrated_error, u_null_ext, u, training_signal)
+        self._keep += [q, dq, target, target_velocity, integrated_error, u_null_ext, u, training_signal, params]
+        self.id = check(lib().abrk_osc_plan_create(arm_id, m.code, C.byref(params), B, *ptrs, *m.where))
 
 
 class SlidingPlan(Plan):
@@ -851,20 +821,10 @@ class SlidingPlan(Plan):
     def __init__(self, arm_id, n, params, q, dq, target, u, target_velocity=None, target_acc=None, s=None,
                  dtype=np.float64, device=0, stream=None):
         Plan.__init__(self, device, stream)
-        a = _Args(dtype)
-        B = q.shape[0]
-        nt = 3 if params.cartesian else n
-        arrs = dict(q=(q, (B, n)), dq=(dq, (B, n)), target=(target, (B, nt)), target_velocity=(target_velocity, (B, nt)),
-                    target_acc=(target_acc, (B, nt)), u=(u, (B, n)), s=(s, (B, n)))
-        ptr = {}
-        for name, (arr, shape) in arrs.items():
-            if arr is not None and not isinstance(arr, DeviceArray):
-                raise TypeError(f"{name}: launch plans take DeviceArrays")
-            ptr[name] = a.inp(arr, shape, name)
-        self._keep += [v[0] for v in arrs.values()] + [params]
-        self.id = check(lib().abrk_sliding_plan_create(
-            arm_id, a.code, C.byref(params), B, ptr["q"], ptr["dq"], ptr["target"], ptr["target_velocity"],
-            ptr["target_acc"], ptr["u"], ptr["s"], device, _sp(stream)))
+        m = _PlanArgs(dtype, device, stream)
+        B, ptrs, _ = _bind_sliding(m, n, params, q, dq, target, target_velocity, target_acc, u, s)
+        self._keep += [q, dq, target, target_velocity, target_acc, u, s, params]
+        self.id = check(lib().abrk_sliding_plan_create(arm_id, m.code, C.byref(params), B, *ptrs, *m.where))
 
 
 class MergedLoops:
@@ -930,12 +890,12 @@ def ik_generate_path(arm_id, n, params, position, target, dtype=np.float64, devi
                      position_path=None, velocity_path=None):
     """InverseKinematics.generate_path for B paths: position [B,n], target [B,6] (xyz + Euler 'sxyz').
     Returns (position_path, velocity_path), each [B, n_timesteps, n]."""
-    a = _Args(dtype)
+    a = _Args(dtype, device)
     B = position.shape[0]
     T = int(params.n_timesteps)
     qp = a.inp(position, (B, n), "position")
     tp = a.inp(target, (B, 6), "target")
-    ppp, ppo = a.out(position_path, (B, T, n), device, "position_path")
-    vpp, vpo = a.out(velocity_path, (B, T, n), device, "velocity_path")
+    ppp, ppo = a.out(position_path, (B, T, n), "position_path")
+    vpp, vpo = a.out(velocity_path, (B, T, n), "velocity_path")
     check(lib().abrk_ik_generate_path_batch(arm_id, a.code, C.byref(params), B, qp, tp, ppp, vpp, device, _sp(stream)))
     return ppo, vpo

@@ -130,6 +130,18 @@ def shard_rows(arrays, rank, world):
     return [None if a is None else a[lo:hi] for a in arrays]
 
 
+def _shard_streams(devices):
+    """the library's own stream of every shard (abrk_shard_stream): the k-th shard on a device runs on that device's
+    slot k - what the *_resident calls use when no streams are named"""
+    from ._lib import shard_stream
+
+    seen, out = {}, []
+    for d in devices:
+        out.append(shard_stream(d, seen.get(d, 0)))
+        seen[d] = seen.get(d, 0) + 1
+    return out
+
+
 class ShardedArray:
     """A [B, ...] array cut into contiguous row shards that LIVE on devices: shard g = rows shard_range(B, g, G) on
     devices[g] (a device may be named several times), each a DeviceArray.  `from_numpy` scatters once, `.numpy()`
@@ -185,22 +197,13 @@ class ShardedArray:
 
     def numpy(self, streams=None):
         """gather: the shards' rows in order, as one host array.  streams[g]: the stream shard g's producer ran on (the
-        copy is enqueued behind it and waited for); None = the library's own shard streams (abrk_shard_stream), which
-        is what the *_resident calls use when no streams are named"""
+        copy is enqueued behind it and waited for); None = the library's own shard streams"""
         import numpy as np
 
-        from ._lib import shard_stream
-
-        out, seen = [], {}
-        for g, (p, d) in enumerate(zip(self.parts, self.devices)):
-            if streams is None:
-                slot = seen.get(d, 0)
-                seen[d] = slot + 1
-                st = shard_stream(d, slot)
-            else:
-                st = streams[g]
-            out.append(p.numpy(st) if p.shape[0] else np.empty(p.shape, p.dtype))
-        return np.concatenate(out)
+        if streams is None:
+            streams = _shard_streams(self.devices)
+        return np.concatenate([p.numpy(st) if p.shape[0] else np.empty(p.shape, p.dtype)
+                               for p, st in zip(self.parts, streams)])
 
     def copy_from_numpy(self, a):
         """overwrite the shards with the rows of a host array (a control loop feeding new states into fixed buffers)"""
@@ -280,13 +283,7 @@ class MultiDevice:
     def streams(self):
         """the stream of every shard: the library's own (device, slot) streams"""
         if self._streams is None:
-            from ._lib import shard_stream
-
-            seen, out = {}, []
-            for d in self.devices:
-                out.append(shard_stream(d, seen.get(d, 0)))
-                seen[d] = seen.get(d, 0) + 1
-            self._streams = out
+            self._streams = _shard_streams(self.devices)
         return self._streams
 
     def scatter(self, a, dtype=None):
@@ -328,12 +325,11 @@ class MultiDevice:
         from . import engine
         from .controllers import OSC
 
-        if not isinstance(ctrlr, OSC) or not getattr(ctrlr, "_fused_config", False) or ctrlr._foreign or ctrlr._device:
-            raise TypeError("record_generate needs an abr_control_amd OSC with fused null controllers only")
+        OSC._fused_only(ctrlr, "record_generate")
         rc = ctrlr.robot_config
         n, B = rc.N_JOINTS, q.shape[0]
         params = ctrlr._params(ref_frame, xyz_offset)
-        ie = self._sharded_state(ctrlr, B, rc.dtype)
+        ie = ctrlr._integral_state(q)
         u = u if u is not None else ShardedArray.empty((B, n), rc.dtype, self.devices, rows=q.rows)
         ts = training_signal
         if ts is True:
@@ -357,37 +353,25 @@ class MultiDevice:
         plan._keep = (q, dq, target, target_velocity, ie, params)
         return plan
 
-    def _sharded_state(self, ctrlr, B, dtype):
-        if ctrlr.ki == 0:
-            return None
-        ie = ctrlr.integrated_error
-        if not isinstance(ie, ShardedArray) or ie.shape != (B, 6) or ie.devices != self.devices:
-            ie = ctrlr.integrated_error = ShardedArray.zeros((B, 6), dtype, self.devices)
-        return ie
-
     def generate(self, ctrlr, q, dq, *args, **kwargs):
-        """ctrlr.generate(q, dq, ...) with the host batch cut over this object's devices.  OSC (fused null controllers),
-        Sliding, Joint, Damping, RestingConfig; arguments and results as the controller's own generate()."""
-        from .controllers import OSC
-
-        if isinstance(q, ShardedArray):
-            return self._generate_resident(ctrlr, q, dq, *args, **kwargs)
-        if isinstance(ctrlr, OSC):
-            return self._generate_osc(ctrlr, q, dq, *args, **kwargs)
-        from .controllers import Damping, Joint, RestingConfig, Sliding
-
-        # (every Controller inherits _joint_generate: the test is the class, not the attribute)
-        if not isinstance(ctrlr, (Sliding, Joint, Damping, RestingConfig)):
-            raise TypeError(f"MultiDevice.generate: {type(ctrlr).__name__} has no sharded entry point")
+        """ctrlr.generate(q, dq, ...) over this object's devices: OSC (fused null controllers), Sliding, Joint, Damping,
+        RestingConfig; arguments and results as the controller's own generate().  A host batch (NumPy) is cut into row
+        shards and comes back whole; ShardedArrays in, ShardedArrays out - the call only enqueues (md.sync() /
+        .numpy() wait), and per-row state (ctrlr.integrated_error, .training_signal, .s) stays with its shards."""
         from ._lib import DeviceArray
+        from .controllers import OSC, Joint, Sliding
+        from .controllers.controller import NullJoint
 
+        if not isinstance(ctrlr, (OSC, Sliding, Joint, NullJoint)):  # (the test is the class, not an attribute)
+            raise TypeError(f"MultiDevice.generate: {type(ctrlr).__name__} has no sharded entry point")
+        run = ctrlr._generate
+        if isinstance(q, ShardedArray):
+            if q.devices != self.devices:
+                raise ValueError("the ShardedArray is cut over other devices than this MultiDevice")
+            return run(self.streams, q, dq, *args, **kwargs)
         if isinstance(q, DeviceArray):
             raise TypeError("MultiDevice takes NumPy arrays (a DeviceArray lives on one device)")
-        ctrlr._shard_devices = self.devices
-        try:
-            return ctrlr.generate(q, dq, *args, **kwargs)
-        finally:
-            ctrlr._shard_devices = None
+        return run(self.devices, q, dq, *args, **kwargs)
 
     def dynamics(self, robot_config, q, dq=None, name="EE", x=None, want=("Tx", "J", "M", "g")):
         """robot_config.dynamics(...) - several robot_config functions from one launch per device - over this
@@ -405,72 +389,6 @@ class MultiDevice:
                                       None if dq2 is None else np.ascontiguousarray(dq2), rc.frame_id(name), xo,
                                       tuple(want), rc.dtype)
         return {k: v[0] for k, v in res.items()} if single else res
-
-    def _generate_resident(self, ctrlr, q, dq, target=None, target_velocity=None, *args, **kwargs):
-        """ShardedArray in, ShardedArray out: the call only enqueues (md.sync() / .numpy() wait)"""
-        from . import engine
-        from .controllers import OSC, Damping, Joint, RestingConfig, Sliding
-
-        rc = ctrlr.robot_config
-        n, B = rc.N_JOINTS, q.shape[0]
-        if q.devices != self.devices:
-            raise ValueError("the ShardedArray is cut over other devices than this MultiDevice")
-        if isinstance(ctrlr, OSC):
-            if not getattr(ctrlr, "_fused_config", False) or ctrlr._foreign or ctrlr._device:
-                raise TypeError("MultiDevice.generate needs an abr_control_amd OSC with fused null controllers only")
-            ref_frame = kwargs.pop("ref_frame", args[0] if args else "EE")
-            xyz_offset = kwargs.pop("xyz_offset", args[1] if len(args) > 1 else None)
-            ie = self._sharded_state(ctrlr, B, rc.dtype)
-            u, ts = engine.osc_generate_resident(rc.arm_id, n, ctrlr._params(ref_frame, xyz_offset), q, dq, target,
-                                                 target_velocity, ie, None, kwargs.pop("u", None), True, rc.dtype,
-                                                 self.streams)
-            ctrlr.training_signal = ts
-            return u
-        from . import _abi
-
-        if isinstance(ctrlr, Sliding):
-            names = ("target_acc", "ref_frame", "offset")
-            kw = dict(zip(names, args))
-            kw.update(kwargs)
-            zero = lambda v: None if (v is None or (not isinstance(v, ShardedArray) and v == 0)) else v
-            params = _abi.make_sliding_params(n, ctrlr.kd, ctrlr.lamb, ctrlr.cartesian, kw.get("ref_frame", "EE"),
-                                              kw.get("offset"))
-            u, s = engine.sliding_generate_resident(rc.arm_id, n, params, q, dq, target, zero(target_velocity),
-                                                    zero(kw.get("target_acc")), None, True, rc.dtype, self.streams)
-            ctrlr.s = s
-            return u
-        if isinstance(ctrlr, RestingConfig):
-            return engine.joint_generate_resident(rc.arm_id, n, ctrlr._ctrl(), False, q, dq, None, None, None, rc.dtype,
-                                                  self.streams)
-        if isinstance(ctrlr, Damping):
-            return engine.joint_generate_resident(rc.arm_id, n, _abi.make_damping(ctrlr.kv), False, q, dq, None, None,
-                                                  None, rc.dtype, self.streams)
-        if isinstance(ctrlr, Joint):
-            return engine.joint_generate_resident(rc.arm_id, n, ctrlr._ctrl(), ctrlr.account_for_gravity, q, dq, target,
-                                                  target_velocity, None, rc.dtype, self.streams)
-        raise TypeError(f"MultiDevice.generate: {type(ctrlr).__name__} has no resident entry point")
-
-    def _generate_osc(self, ctrlr, q, dq, target, target_velocity=None, ref_frame="EE", xyz_offset=None):
-        import numpy as np
-
-        from . import engine
-
-        rc = ctrlr.robot_config
-        if not getattr(ctrlr, "_fused_config", False) or ctrlr._foreign or ctrlr._device:
-            raise TypeError("MultiDevice.generate needs an abr_control_amd OSC with fused null controllers only")
-        (q2, dq2, t2, tv2), single = ctrlr._rows(q, dq, target, target_velocity)
-        B = q2.shape[0]
-        ie = None
-        if ctrlr.ki != 0:
-            ie = ctrlr._host_integrated_error(B, rc.dtype)  # a single state's (6,) is kept, as in OSC.generate
-        u, ts = engine.osc_generate_sharded(rc.arm_id, rc.N_JOINTS, ctrlr._params(ref_frame, xyz_offset), q2, dq2, t2,
-                                            self.devices, tv2, ie, training_signal=True, dtype=rc.dtype)
-        if ctrlr.ki != 0:
-            ctrlr.integrated_error = ie[0] if single else ie
-        if rc.reference_dtypes:
-            u, ts = u.astype(np.float64), ts.astype(np.float64)
-        ctrlr.training_signal = ts[0] if single else ts
-        return u[0] if single else u
 
 
 class _CutOnly:
