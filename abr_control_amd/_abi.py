@@ -400,6 +400,44 @@ def lif_gain_bias(intercepts, max_rates, tau_rc=0.02, tau_ref=0.002):
     return gain, 1.0 - gain * intercepts
 
 
+CHANNEL_MAX_WIDTH, CHANNEL_MAX_DELAY = 16, 4096  # ABRK_CHANNEL_* (include/abrk.h)
+
+
+class ChannelParams(C.Structure):
+    """abrk_channel_params (include/abrk.h)"""
+    _fields_ = [("width", C.c_int32), ("delay", C.c_int32), ("seed", C.c_uint64), ("row_offset", C.c_int64),
+                ("dt", C.c_double), ("tau_diff", C.c_double), ("bias", C.c_double * CHANNEL_MAX_WIDTH),
+                ("sigma", C.c_double * CHANNEL_MAX_WIDTH), ("resolution", C.c_double * CHANNEL_MAX_WIDTH)]
+
+
+class ChannelState(C.Structure):
+    """abrk_channel_state (include/abrk.h): the tick counter and the three per-row state arrays"""
+    _fields_ = [(k, C.c_void_p) for k in ("counter", "ring", "prev", "d_f")]
+
+
+def make_channel_params(width, bias=0.0, sigma=0.0, resolution=0.0, delay=0, seed=0, row_offset=0, dt=0.001,
+                        tau_diff=0.0):
+    """Parameters of sensing.channel_step: `width` columns; bias, sigma (noise standard deviation) and resolution
+    (quantisation step) are scalars or one value per column; delay in whole ticks; seed (uint64) and row_offset (the
+    global number of row 0) select the noise; dt and tau_diff belong to the differenced output.  The values are checked
+    by the C entry point; only what cannot be stored is refused here."""
+    width = int(width)
+    if not 1 <= width <= CHANNEL_MAX_WIDTH:
+        raise ValueError(f"width={width} outside 1..{CHANNEL_MAX_WIDTH}")
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"seed={seed} is not a 64-bit unsigned value")
+    p = ChannelParams()
+    p.width, p.delay = width, int(delay)
+    p.seed, p.row_offset = int(seed), int(row_offset)
+    p.dt, p.tau_diff = float(dt), float(tau_diff)
+    for name, val in (("bias", bias), ("sigma", sigma), ("resolution", resolution)):
+        col = np.asarray(val, dtype=float)
+        if col.ndim > 1 or (col.ndim == 1 and col.shape[0] != width):
+            raise ValueError(f"{name}: a scalar or {width} values, got shape {col.shape}")
+        getattr(p, name)[:width] = np.broadcast_to(col, (width,)).tolist()
+    return p
+
+
 TABLE_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "arms", "tables")
 BUILTIN_ARMS = ("ur5", "jaco2", "twojoint", "threejoint", "onejoint")
 

@@ -111,6 +111,8 @@ def lib():
             C.c_int, _vp]
         L.abrk_adapt_step_batch.argtypes = [C.c_int, C.POINTER(_abi.AdaptParams), _i64] + [_vp] * 6 + [
             C.c_int32, _vp, C.c_int32, _vp, C.POINTER(_abi.AdaptState), _vp, _vp, C.c_int, _vp]
+        L.abrk_channel_step_batch.argtypes = [C.c_int, C.POINTER(_abi.ChannelParams), _i64, _vp, C.c_int32, _vp,
+                                              C.c_int32, _vp, _vp, _vp, C.POINTER(_abi.ChannelState), C.c_int, _vp]
         L.abrk_osc_rollout_twolink_batch.argtypes = [
             C.c_int, C.c_int, C.POINTER(_abi.OSCParams), C.POINTER(_abi.TwoLinkPlant), _i64, C.c_int32, C.c_int32,
             _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]

@@ -27,6 +27,7 @@
 #include "abrk_params.h"
 #include "abrk_path.h"
 #include "abrk_adapt.h"
+#include "abrk_channel.h"
 
 namespace abrk {
 const ArmOps* ops_ur5();
@@ -2460,6 +2461,76 @@ extern "C" int abrk_adapt_step_batch(int dtype, const abrk_adapt_params* P, int6
   const hipStream_t hs = (hipStream_t)stream;
   return dispatch(st, nullptr, dtype, [=](const void*) {
     return dtype == ABRK_F64 ? launch_adapt_step(type, a64, hs) : launch_adapt_step(type, a32, hs);
+  });
+}
+
+// ------------------------------------------------------------------------------- measurement channel
+namespace {
+struct ChannelPtrs {
+  const void *in0, *in1;
+  void *out0, *out1, *dy, *counter, *ring, *prev, *d_f;
+};
+template <class T>
+ChannelArgs<T> bind_channel(const abrk_channel_params& P, int64_t B, int w0, int w1, const ChannelPtrs& p) {
+  ChannelArgs<T> a = channel_make_args<T>(w0, w1, P.delay, (long)B, P.seed, P.row_offset, P.dt, P.tau_diff, P.bias,
+                                          P.sigma, P.resolution);
+  a.in0 = (const T*)p.in0;
+  a.in1 = (const T*)p.in1;
+  a.out0 = (T*)p.out0;
+  a.out1 = (T*)p.out1;
+  a.dy = (T*)p.dy;
+  a.counter = (int32_t*)p.counter;
+  a.ring = (T*)p.ring;
+  a.prev = (T*)p.prev;
+  a.d_f = (T*)p.d_f;
+  return a;
+}
+}  // namespace
+
+extern "C" int abrk_channel_step_batch(int dtype, const abrk_channel_params* P, int64_t B, const void* in0, int32_t w0,
+                                       const void* in1, int32_t w1, void* out0, void* out1, void* dy,
+                                       const abrk_channel_state* S, int device, void* stream) {
+  if (dtype != ABRK_F64 && dtype != ABRK_F32) return fail(ABRK_EINVAL, "dtype %d is not ABRK_F64/ABRK_F32", dtype);
+  if (!P || !S) return fail(ABRK_EINVAL, "params and state are required");
+  if (B < 0 || B > 2147483647) return fail(ABRK_EINVAL, "batch %lld outside 0..2^31-1", (long long)B);
+  if (P->width < 1 || P->width > ABRK_CHANNEL_MAX_WIDTH)
+    return fail(ABRK_EINVAL, "width=%d outside 1..%d", P->width, ABRK_CHANNEL_MAX_WIDTH);
+  if (P->delay < 0 || P->delay > ABRK_CHANNEL_MAX_DELAY)
+    return fail(ABRK_EINVAL, "delay=%d outside 0..%d", P->delay, ABRK_CHANNEL_MAX_DELAY);
+  if (w0 < 1 || w1 < 0 || (int64_t)w0 + w1 != P->width)
+    return fail(ABRK_EINVAL, "widths %d + %d do not make width=%d", w0, w1, P->width);
+  if (w1 > 0 && (!in1 || !out1)) return fail(ABRK_EINVAL, "in1 and out1 are required when w1 > 0");
+  for (int c = 0; c < P->width; c++) {
+    if (!nonnegative_finite_at(&P->sigma[c])) return fail(ABRK_EINVAL, "sigma[%d] is negative or not finite", c);
+    if (!nonnegative_finite_at(&P->resolution[c])) return fail(ABRK_EINVAL, "resolution[%d] is negative or not finite", c);
+    if (!finite_at(&P->bias[c])) return fail(ABRK_EINVAL, "bias[%d] is not finite", c);
+  }
+  if (!positive_finite_at(&P->dt)) return fail(ABRK_EINVAL, "dt=%g is not a positive finite step", P->dt);
+  if (dy && !nonnegative_finite_at(&P->tau_diff)) return fail(ABRK_EINVAL, "tau_diff=%g is negative or not finite", P->tau_diff);
+  if (!in0 || !out0) return fail(ABRK_EINVAL, "in0 and out0 are required");
+  if (!S->counter) return fail(ABRK_EINVAL, "counter is NULL");
+  if (P->delay > 0 && !S->ring) return fail(ABRK_EINVAL, "delay=%d needs the ring", P->delay);
+  if (dy && (!S->prev || !S->d_f)) return fail(ABRK_EINVAL, "dy needs prev and d_f");
+  if (B == 0) return 0;
+  if (int rc = use_device(device)) return rc;
+  const size_t s = esz(dtype), W = (size_t)P->width;
+  Stager st{device, (hipStream_t)stream};
+  ChannelPtrs p{};
+  st.in(&p.in0, in0, (size_t)B * w0 * s);
+  st.in(&p.in1, w1 > 0 ? in1 : nullptr, (size_t)B * w1 * s);
+  st.out(&p.out0, out0, (size_t)B * w0 * s);
+  st.out(&p.out1, w1 > 0 ? out1 : nullptr, (size_t)B * w1 * s);
+  st.out(&p.dy, dy, (size_t)B * W * s);
+  st.inout(&p.counter, S->counter, (size_t)B * 4);
+  st.inout(&p.ring, P->delay > 0 ? S->ring : nullptr, ((size_t)P->delay + 1) * B * W * s);
+  st.inout(&p.prev, dy ? S->prev : nullptr, (size_t)B * W * s);
+  st.inout(&p.d_f, dy ? S->d_f : nullptr, (size_t)B * W * s);
+  if (int rc = st.reserve()) return rc;
+  const ChannelArgs<double> a64 = bind_channel<double>(*P, B, w0, w1, p);
+  const ChannelArgs<float> a32 = bind_channel<float>(*P, B, w0, w1, p);
+  const hipStream_t hs = (hipStream_t)stream;
+  return dispatch(st, nullptr, dtype, [=](const void*) {
+    return dtype == ABRK_F64 ? launch_channel_step(a64, hs) : launch_channel_step(a32, hs);
   });
 }
 

@@ -532,6 +532,62 @@ int abrk_adapt_step_batch(int dtype, const abrk_adapt_params* params, int64_t B,
                           void* u_add, int device, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * The measurement and actuation channel of a recorded loop: a [B, W] signal passed through bias, noise, quantisation,
+ * latency and an optional filtered difference, one tick per call.  The same call serves the sensing side (q, dq -> what
+ * the law reads) and the actuation side (u -> what the plant receives).  All arrays are of `dtype` but counter (int32).
+ * With t = max(counter[b], 0), d = delay, x = concat(in0[b], in1[b])[c] (in0 [B,w0], in1 [B,w1] or NULL, w0 + w1 = width),
+ * one tick of row b, column c is
+ *   1  v = fma(sigma[c], n, x + bias[c])               n: the standard normal below.  sigma[c] == 0: no number is drawn
+ *                                                      and v = x + bias[c]
+ *   2  resolution[c] > 0: v = rint(v * inv_res[c]) * resolution[c]        inv_res = 1 / resolution formed in double and
+ *                                                      rounded to `dtype`; rint rounds half to even
+ *   3  d > 0: ring[t % (d + 1), b, c] = v, then out = ring[max(t - d, 0) % (d + 1), b, c]      ring [d + 1, B, width],
+ *      time-major: a tick's rows are contiguous.  For t < d that is the sample of tick 0: the channel holds its first
+ *      sample.  d == 0: out = v; the ring is neither read nor written and may be NULL
+ *   4  out -> out0[b, c] or out1[b, c - w0], mirroring the inputs
+ *   5  only when dy [B,width] is given: at t == 0 g = 0 and d_f = 0, otherwise g = (out - prev[b,c]) / dt (a product with
+ *      1 / dt) and d_f = fma(a, g - d_f, d_f) with a = 1 - exp(-dt / tau_diff), a = 1 for tau_diff = 0 (formed in double);
+ *      dy[b,c] = d_f, prev[b,c] = out                   prev, d_f [B,width]
+ *   6  counter[b] = t + 1
+ * Zero filling counter - of all rows or of some - restarts them; nothing else needs clearing, since tick 0 reads nothing
+ * it has not written.  With sigma = bias = resolution = 0, delay = 0 and no dy the call returns x bit for bit.
+ * n is computed in fp64 whatever `dtype` is and rounded to `dtype` at the fma (fp32 sees the same realisation):
+ * Philox4x32-10 - multipliers 0xD2511F53 on word 0 and 0xCD9E8D57 on word 2, one round [hi(M1 c2) ^ c1 ^ k0, lo(M1 c2),
+ * hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)], key increments 0x9E3779B9 and 0xBB67AE85 - with the key (seed low 32, seed high 32)
+ * and the counter (r low 32, r high 32, t, c), r = b + row_offset as a 64-bit value.  From the output words w0..w3:
+ * k1 = (w0 >> 5) 2^26 + (w1 >> 6), k2 likewise from w2, w3; u1 = (k1 + 1) 2^-53 in (0, 1], u2 = k2 2^-53;
+ * n = sqrt(-2 ln u1) cos(2 pi u2).  n depends on (seed, global row, tick, column) alone: a row's bits do not depend on
+ * the batch it arrives in, and a shard continues the numbering through row_offset.
+ * Goes through the staging of every *_batch call (host arrays work for one-off calls) and is recorded between
+ * abrk_plan_begin and abrk_plan_end: in { channel(q, dq -> q_meas, dq_meas); law on q_meas, dq_meas; channel(u -> u_act);
+ * plant step on u_act } the state lives in device memory and advances at every replay.
+ * ABRK_EINVAL: dtype; B < 0; width outside 1..ABRK_CHANNEL_MAX_WIDTH; delay outside 0..ABRK_CHANNEL_MAX_DELAY; w0 + w1 !=
+ * width; w1 != 0 with in1 or out1 NULL; a sigma or resolution that is negative or not finite, a bias that is not finite;
+ * dt <= 0; with dy, a tau_diff that is negative or not finite; NULL params, in0, out0, state or counter; NULL ring with
+ * delay > 0; NULL prev or d_f with dy.  B == 0 returns before the device is touched.
+ * --------------------------------------------------------------------------------- */
+#define ABRK_CHANNEL_MAX_WIDTH 16
+#define ABRK_CHANNEL_MAX_DELAY 4096
+typedef struct abrk_channel_params {
+  int32_t width;      /* W, 1..ABRK_CHANNEL_MAX_WIDTH */
+  int32_t delay;      /* whole ticks, 0..ABRK_CHANNEL_MAX_DELAY */
+  uint64_t seed;
+  int64_t row_offset; /* global number of row 0 */
+  double dt;
+  double tau_diff;    /* low-pass of the difference; 0: none */
+  double bias[ABRK_CHANNEL_MAX_WIDTH];
+  double sigma[ABRK_CHANNEL_MAX_WIDTH];      /* noise standard deviation; 0: none */
+  double resolution[ABRK_CHANNEL_MAX_WIDTH]; /* quantisation step; 0: none */
+} abrk_channel_params;
+typedef struct abrk_channel_state {
+  void* counter;           /* int32 [B] */
+  void *ring, *prev, *d_f; /* [delay + 1, B, width], [B,width], [B,width] */
+} abrk_channel_state;
+int abrk_channel_step_batch(int dtype, const abrk_channel_params* params, int64_t B, const void* in0, int32_t w0,
+                            const void* in1, int32_t w1, void* out0, void* out1, void* dy,
+                            const abrk_channel_state* state, int device, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * The output side of a recorded loop: what every closed-loop example of the reference keeps in ee_track / target_track /
  * q_track lists and reduces with np.linalg.norm(ee - target), kept on the device.  One call = one tick of every row.  With
  * t = counter[b]:
