@@ -78,6 +78,56 @@ def test_resident_entry_points_validate_and_fail_loudly_without_a_device(L):
         assert not L.abrk_shard_stream(0, 0)
 
 
+def test_sharded_families_require_their_arrays_in_every_form(L):
+    """OSC, Sliding, Joint and dynamics in their three forms: every required array missing in turn is ABRK_EINVAL with a
+    message from *_batch, *_sharded and *_resident (there the whole pointer table is NULL), and a zero-row batch is a
+    no-op for *_batch and *_sharded.  No device is needed: the checks come before one is touched."""
+    ur5, f64, B = L.abrk_arm_builtin(b"ur5"), _abi.F64, 4
+    buf = np.zeros((B, 36))  # stands for any array of a call (the widest, M, has 6 * 6 values per row)
+    ptr = buf.ctypes.data
+    devices = (C.c_int * 1)(0)
+    cut = _abi.ShardCut(1, (C.c_int32 * 1)(0), (C.c_int64 * 1)(B), None)
+    tab = (C.c_void_p * 1)(ptr)
+    posc, psl, pj = _abi.make_osc_params(6, kp=10), _abi.make_sliding_params(6), _abi.make_joint(kp=2)
+    ee, want = _abi.frame_id("EE", 6), _abi.WANT_M
+
+    def dyn_out(m):  # one abrk_dyn_out (per shard) with M alone, or no struct at all
+        return C.byref(_abi.DynOut(M=m)) if m else None
+
+    # name -> (number of arrays, indices of the required ones, batch(arrays, B), sharded(arrays, B), resident(tables))
+    families = {
+        "osc": (8, (0, 1, 2, 6),
+                lambda a, b: L.abrk_osc_generate_batch(ur5, f64, C.byref(posc), b, *a, 0, None),
+                lambda a, b: L.abrk_osc_generate_sharded(ur5, f64, C.byref(posc), b, *a, 1, devices),
+                lambda t: L.abrk_osc_generate_resident(ur5, f64, C.byref(posc), C.byref(cut), *t)),
+        "sliding": (7, (0, 1, 2, 5),
+                    lambda a, b: L.abrk_sliding_generate_batch(ur5, f64, C.byref(psl), b, *a, 0, None),
+                    lambda a, b: L.abrk_sliding_generate_sharded(ur5, f64, C.byref(psl), b, *a, 1, devices),
+                    lambda t: L.abrk_sliding_generate_resident(ur5, f64, C.byref(psl), C.byref(cut), *t)),
+        "joint": (5, (0, 1, 4),
+                  lambda a, b: L.abrk_joint_generate_batch(ur5, f64, C.byref(pj), 1, b, *a, 0, None),
+                  lambda a, b: L.abrk_joint_generate_sharded(ur5, f64, C.byref(pj), 1, b, *a, 1, devices),
+                  lambda t: L.abrk_joint_generate_resident(ur5, f64, C.byref(pj), 1, C.byref(cut), *t)),
+        # (q, dq, M): M is the one output asked for
+        "dynamics": (3, (0, 2),
+                     lambda a, b: L.abrk_dynamics_batch(ur5, f64, b, a[0], a[1], ee, None, want, dyn_out(a[2]), 0, None),
+                     lambda a, b: L.abrk_dynamics_sharded(ur5, f64, b, a[0], a[1], ee, None, want, dyn_out(a[2]), 1,
+                                                          devices),
+                     lambda t: L.abrk_dynamics_resident(ur5, f64, C.byref(cut), t[0], t[1], ee, None, want,
+                                                        dyn_out(t[2] and ptr))),
+    }
+    for name, (n_arrays, required, batch, sharded, resident) in families.items():
+        for missing in required:
+            arrays = [None if k == missing else ptr for k in range(n_arrays)]
+            tables = [None if k == missing else tab for k in range(n_arrays)]
+            for form, rc in (("batch", batch(arrays, B)), ("sharded", sharded(arrays, B)), ("resident", resident(tables))):
+                assert rc == -1 and L.abrk_last_error(), (name, form, missing, rc)  # ABRK_EINVAL
+        assert batch([ptr] * n_arrays, 0) == 0 and sharded([ptr] * n_arrays, 0) == 0, name
+    # Joint.generate (kind 0) also needs target, which Damping and RestingConfig do not
+    no_target = [ptr, ptr, None, ptr, ptr]
+    assert families["joint"][2](no_target, B) == -1 and families["joint"][3](no_target, B) == -1
+
+
 def test_sharded_array_cut_matches_shard_range():
     from abr_control_amd.sharding import ShardedArray, shard_range
 

@@ -2133,6 +2133,83 @@ def test_gpu_sharded_sliding_joint_dynamics_equal_unsharded_bitwise():
         engine.dynamics_sharded(be.arm_id, 6, q, [0], None, None, None, ("C",))  # C needs dq
 
 
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_gpu_batch_sharded_and_resident_forms_agree_for_every_set_of_optional_arrays(dtype):
+    """The three forms of the four sharded families read one table of the family's arrays: `*_batch` on host arrays,
+    `*_sharded` and `*_resident` are `array_equal` for every set of optional arrays, i.e. wherever an array is absent
+    in the middle of the list.  UR5, 131 rows over devices [0, 0, 0]: shards of 44, 44 and 43 rows, none a whole
+    wavefront.  OSC runs two ticks each, so that the in/out integral state is compared too."""
+    from itertools import product
+
+    from abr_control_amd import engine
+    from abr_control_amd.sharding import MultiDevice
+
+    arm, B, devices = cases.GpuBackend("ur5").arm_id, 131, [0, 0, 0]
+    md = MultiDevice(devices)
+    rs = np.random.RandomState(133)
+    q, dq, t = (x.astype(dtype) for x in draw(131, B, 6))
+    tv, une, ta = (rs.uniform(-0.5, 0.5, (B, 6)).astype(dtype) for _ in range(3))
+    qs, dqs, ts_, tvs, unes, tas = (md.scatter(x) for x in (q, dq, t, tv, une, ta))
+    assert qs.rows == [44, 44, 43]
+
+    def same(batch, sharded, resident, what):
+        for b, s, r in zip(*((x if isinstance(x, tuple) else (x,)) for x in (batch, sharded, resident))):
+            assert np.array_equal(s, b) and np.array_equal(r.numpy(), b), what
+
+    def osc(dof, with_tv, with_ie, with_une, with_ts):
+        what = (dof, with_tv, with_ie, with_une, with_ts)
+        p = _abi.make_osc_params(6, kp=100, ko=80, kv=15, ki=0.2 if with_ie else 0, ctrlr_dof=dof)
+        ie_b, ie_s = (np.zeros((B, 6), dtype) if with_ie else None for _ in range(2))
+        ie_r = md.scatter(np.zeros((B, 6), dtype)) if with_ie else None
+        pick = lambda use, x: x if use else None
+        for tick in range(2):
+            kw = dict(training_signal=with_ts, dtype=dtype)
+            same(engine.osc_generate(arm, 6, p, q, dq, t, pick(with_tv, tv), ie_b, pick(with_une, une), **kw),
+                 engine.osc_generate_sharded(arm, 6, p, q, dq, t, devices, pick(with_tv, tv), ie_s, pick(with_une, une), **kw),
+                 engine.osc_generate_resident(arm, 6, p, qs, dqs, ts_, pick(with_tv, tvs), ie_r, pick(with_une, unes), **kw),
+                 what + (tick,))
+            if with_ie:
+                assert ie_b.any() and np.array_equal(ie_s, ie_b) and np.array_equal(ie_r.numpy(), ie_b), what + (tick,)
+
+    for subset in product((False, True), repeat=4):
+        osc([1, 1, 1, 0, 0, 0], *subset)
+    osc([1] * 6, True, True, True, True)
+
+    ps = _abi.make_sliding_params(6)
+    for with_tv, with_ta, with_s in product((False, True), repeat=3):
+        pick = lambda use, x: x[:, :3] if use else None
+        tv3, ta3, tvs3, tas3 = pick(with_tv, tv), pick(with_ta, ta), None, None
+        if with_tv:
+            tvs3 = md.scatter(tv3)
+        if with_ta:
+            tas3 = md.scatter(ta3)
+        same(engine.sliding_generate(arm, 6, ps, q, dq, t[:, :3], tv3, ta3, want_s=with_s, dtype=dtype),
+             engine.sliding_generate_sharded(arm, 6, ps, q, dq, t[:, :3], devices, tv3, ta3, want_s=with_s, dtype=dtype),
+             engine.sliding_generate_resident(arm, 6, ps, qs, dqs, md.scatter(t[:, :3]), tvs3, tas3, want_s=with_s,
+                                              dtype=dtype),
+             ("sliding", with_tv, with_ta, with_s))
+
+    for ctrl, target, velocity in ((_abi.make_joint(50, 7), True, True), (_abi.make_joint(50, 7), True, False),
+                                   (_abi.make_damping(10), False, False)):
+        pick = lambda use, x: x if use else None
+        same(engine.joint_generate(arm, 6, ctrl, True, q, dq, pick(target, t), pick(velocity, tv), dtype=dtype),
+             engine.joint_generate_sharded(arm, 6, ctrl, True, q, dq, devices, pick(target, t), pick(velocity, tv),
+                                           dtype=dtype),
+             engine.joint_generate_resident(arm, 6, ctrl, True, qs, dqs, pick(target, ts_), pick(velocity, tvs),
+                                            dtype=dtype),
+             ("joint", ctrl.kind, target, velocity))
+
+    frame, x_off = _abi.frame_id("link4", 6), [0.1, -0.05, 0.2]
+    every = ("Tx", "J", "M", "g", "C", "dJ", "R", "T", "Tinv", "quat")
+    for want, with_dq in ((every, True), (("M",), False), (("Tx", "dJ", "quat"), True)):
+        b = engine.dynamics(arm, 6, q, dq if with_dq else None, frame, x_off, want, dtype)
+        s = engine.dynamics_sharded(arm, 6, q, devices, dq if with_dq else None, frame, x_off, want, dtype)
+        r = engine.dynamics_resident(arm, 6, qs, dqs if with_dq else None, frame, x_off, want, dtype)
+        assert set(b) == set(s) == set(r) == set(want)
+        for k in want:
+            assert np.array_equal(s[k], b[k]) and np.array_equal(r[k].numpy(), b[k]), (want, k)
+
+
 # ---------------------------------------------------------------------------- the wave-cooperative mapping (north_star)
 @pytest.mark.parametrize("lanes", [4, 8, 16])
 def test_gpu_wave_cooperative_variant_matches_reference_and_lane_per_arm(lanes):
