@@ -102,6 +102,11 @@ def lib():
                                                      _vp, _vp, _vp, _vp, C.c_int, _vp]
         L.abrk_plant_step_fx_batch.argtypes = [C.c_int, C.c_int, C.POINTER(_abi.PlantParams),
                                                C.POINTER(_abi.PlantEffects), _i64, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]
+        L.abrk_forward_dynamics_payload_batch.argtypes = [C.c_int, C.c_int, C.POINTER(_abi.PlantEffects), _i64, _vp, _vp,
+                                                          _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]
+        L.abrk_plant_step_payload_batch.argtypes = [C.c_int, C.c_int, C.POINTER(_abi.PlantParams),
+                                                    C.POINTER(_abi.PlantEffects), _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                    C.c_int, _vp]
         L.abrk_path_plan_batch.argtypes = [C.POINTER(_abi.PathParams), _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, C.c_int,
                                            _vp]
         L.abrk_path_fill_batch.argtypes = [C.POINTER(_abi.PathParams), _vp, _vp, _i64, C.c_int32] + [_vp] * 8 + [

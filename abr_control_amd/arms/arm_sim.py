@@ -4,14 +4,16 @@ connect / disconnect / reset / get_feedback / send_forces, for one arm (q of sha
 dq += ddq h, q += dq h, `substeps` times per call with h = dt / substeps (arms/threejoint/arm_sim.py:93-94 takes
 dt / 1e-5 such substeps).  `effects` (_abi.make_plant_effects) makes the plant non-ideal: torque saturation, viscous and
 smoothed Coulomb joint friction, hard joint limits with restitution; send_forces also takes a joint-space disturbance
-`tau_ext` and a world-frame wrench at the end effector (include/abrk.h, abrk_plant_effects).  No contacts."""
+`tau_ext` and a world-frame wrench at the end effector (include/abrk.h, abrk_plant_effects).  `payload` is a point mass
+carried at the end effector - (m, r) for every arm, or [B, 4] rows of m, rx, ry, rz - which changes M, C and g of the
+plant and which the robot_config (the controller's model) knows nothing of.  No contacts."""
 import numpy as np
 
-from .. import _abi, engine
+from .. import _abi, engine, plant_payload
 
 
 class ArmSim:
-    def __init__(self, robot_config, dt=0.001, q_init=None, substeps=1, gravity=True, effects=None):
+    def __init__(self, robot_config, dt=0.001, q_init=None, substeps=1, gravity=True, effects=None, payload=None):
         self.robot_config = robot_config
         n = robot_config.N_JOINTS
         q0 = q_init if q_init is not None else getattr(robot_config, "START_ANGLES", None)
@@ -22,8 +24,29 @@ class ArmSim:
         self.substeps = int(substeps)
         self.gravity = bool(gravity)
         self.effects = effects
+        self.payload = self._payload_rows(payload)
         self.t = 0.0
         self.reset()
+
+    @staticmethod
+    def _payload_rows(payload):
+        """None, (m, r) with r of three values, or [B, 4] / (4,) of m, rx, ry, rz -> None or a float array [.., 4]"""
+        if payload is None:
+            return None
+        if isinstance(payload, tuple) and len(payload) == 2 and np.ndim(payload[0]) == 0:
+            m, r = payload
+            r = np.asarray(r, dtype=float)
+            if r.shape != (3,):
+                raise ValueError(f"payload offset has shape {r.shape}; expected (3,)")
+            return np.concatenate([[float(m)], r])
+        p = np.asarray(payload, dtype=float)
+        if p.ndim not in (1, 2) or p.shape[-1] != 4:
+            raise ValueError(f"payload has shape {p.shape}; expected (m, r), (4,) or (B, 4)")
+        return p
+
+    def set_payload(self, payload):
+        """the payload carried from the next step on: None, (m, r), (4,) or (B, 4) of m, rx, ry, rz"""
+        self.payload = self._payload_rows(payload)
 
     def connect(self):
         self.reset()
@@ -40,7 +63,7 @@ class ArmSim:
 
     def send_forces(self, u, dt=None, tau_ext=None, wrench=None):
         """advance one time step under torques u (arm_sim.py:67-82); tau_ext (n,) or (B, n) and wrench (6,) or (B, 6) are
-        loads the controller does not know of"""
+        loads the controller does not know of; the payload carried is self.payload (set_payload changes it between steps)"""
         rc = self.robot_config
         dtype = np.dtype(getattr(rc, "dtype", np.float64))
         single = self.q.ndim == 1
@@ -54,7 +77,8 @@ class ArmSim:
                 return None
             return np.ascontiguousarray(np.broadcast_to(np.atleast_2d(np.asarray(x, dtype=dtype)), (q.shape[0], w)))
 
-        engine.plant_step(rc.arm_id, rc.N_JOINTS, params, q, dq, u2, dtype=dtype, device=rc.device, effects=self.effects,
-                          tau_ext=rows(tau_ext, q.shape[1]), wrench=rows(wrench, 6))
+        plant_payload.plant_step(rc.arm_id, rc.N_JOINTS, params, q, dq, u2, dtype=dtype, device=rc.device,
+                                 effects=self.effects, tau_ext=rows(tau_ext, q.shape[1]), wrench=rows(wrench, 6),
+                                 payload=rows(self.payload, 4))
         self.q, self.dq = (q[0], dq[0]) if single else (q, dq)
         self.t += self.dt

@@ -2354,6 +2354,222 @@ ABRK_INL void plant_fx_row(const A& arm, T h, int substeps, bool gravity, bool i
   }
 }
 
+// ---------------------------------------------------------------- the plant with a payload at the end effector, one row
+// plant_fx_row plus a point mass m >= 0 at offset r from the origin of the EE frame, in that frame's coordinates (the x of
+// robot_config.Tx("EE", q, x=r)): the arm with one more link of _M_LINKS = diag(m, m, m, 0, 0, 0) whose centre of mass is
+// that point.  With Jp = J("EE", q, x=r)[:3] and dJp = dJ("EE", q, dq, x=r)[:3], per substep (include/abrk.h):
+//   ddq = (M + m Jp^T Jp)^-1 (tau - C dq - m Jp^T (dJp dq) - g - Jp^T m (0, 0, -9.81)^T)
+// A row program of its own: plant_row and plant_fx_row stay as they are, symbol for symbol.  The phases of plant_fx_row,
+// with two additions.  A: the kinematics chain that serves the wrench also gives the point, Jp (jacobian) and the bias
+// acceleration dJp dq (jacobian_dot); -m Jp^T (dJp dq + (0, 0, -9.81)) joins the parked tau, and sqrt(m) Jp - 3 N values -
+// is parked beside it (`jpark`), since nothing may live across the dynamics pass (profiles/plant_step.md).  B: after the
+// pass the parked factor comes back and (sqrt(m) Jp)^T (sqrt(m) Jp) is added to M ahead of chol, so minpiv is a pivot of
+// the augmented matrix.  No branch on m: m = 0 is the neutral value (the row then differs from plant_fx_row by the
+// rounding of additions of zero only where the compiler orders the dynamics pass differently - phase A reads dq here).
+// `get_load` hands out the row's m, rx, ry, rz; it is called in every substep, like get_u.
+template <class A, class T, class GetU, class GetExt, class GetW, class GetLoad, class Scr>
+ABRK_INL void plant_load_row(const A& arm, T h, int substeps, bool gravity, bool integrate, const T* fxc,
+                             T (&q)[A::N], T (&dq)[A::N], GetU&& get_u, GetExt&& get_ext, GetW&& get_w,
+                             GetLoad&& get_load, const FxPark<T>& park, const FxPark<T>& jpark, T (&ddq)[A::N],
+                             T& minpiv, Scr& scr) {
+  constexpr int N = A::N;
+  using F = PlantFxP<T>;
+  static_assert(N <= F::kJ, "PlantFxP holds kJ constants per effect");
+  constexpr bool REC = kRecursiveC<A, CMODE_VEC>;
+  const T gacc = gravity ? T(-9.81) : T(0);  // uniform: the z component of the payload's gravity term
+  auto park_friction = [&](const T(&dqv)[N]) ABRK_LAMBDA {
+    const T* c = reread(fxc);
+    sfor<N>([&](auto i) ABRK_LAMBDA {
+      const T ir = Rm<T>::rsqrt(Rm<T>::fma(dqv[i()], dqv[i()], c[F::VS2]));
+      park.p[i() * park.stride] = Rm<T>::fma(-c[F::COUL + i()] * dqv[i()], ir, -c[F::DAMP + i()] * dqv[i()]);
+    });
+  };
+  park_friction(dq);
+  for (int s = 0; s < substeps; s++) {
+    NoCap nc;
+    // ---- A: tau, the payload's share of it, and sqrt(m) Jp
+    {
+      T tau[N], ext[N];
+      const T* c = reread(fxc);
+      get_u(tau);
+      sfor<N>([&](auto i) ABRK_LAMBDA {
+        tau[i()] = Rm<T>::fmin(Rm<T>::fmax(tau[i()], -c[F::TMAX + i()]), c[F::TMAX + i()]);
+      });
+      get_ext(ext);
+      sfor<N>([&](auto i) ABRK_LAMBDA { tau[i()] = Rm<T>::fma(c[F::ON_EXT], ext[i()], tau[i()]); });
+      {
+        // (copies of sin / cos the optimiser knows nothing of, as in plant_fx_row: this chain stays apart from phase B's)
+        Joints<A, T> jk;
+        T KR[9], ko[3], RE[9], pe[3], w[6], sk[N][2];
+        bool in_a = true;
+        sfor<N>([&](auto i) ABRK_LAMBDA {
+          T qa = q[i()];
+          opaque(qa);
+          if constexpr (std::remove_reference<Scr>::type::kHasTab) {
+            in_a = in_a && Rm<T>::sincos_tab_in_range(qa);
+            Rm<T>::sincos_tab(qa, scr.sctab, sk[i()][0], sk[i()][1]);
+          } else {
+            in_a = in_a && Rm<T>::sincos_in_range(qa);
+            Rm<T>::sincos_fast(qa, sk[i()][0], sk[i()][1]);
+          }
+        });
+        if (!in_a)
+          sfor<N>([&](auto i) ABRK_LAMBDA {
+            const SinCosPair<T> r = sincos_out_of_line(q[i()]);
+            sk[i()][0] = r.s;
+            sk[i()][1] = r.c;
+          });
+        fk_forward(arm, q, jk, KR, ko, nc, [](auto, const T(&)[3]) ABRK_LAMBDA {}, ScUse<T, N>{sk});
+        mulBE<A, T>(arm, KR, ko, RE, pe);
+        // the payload's point, right away: the frame's rotation is not needed again
+        T ld[4], pp[3];
+        get_load(ld);
+        sfor<3>([&](auto r) ABRK_LAMBDA {
+          pp[r()] = pe[r()] + (RE[r() * 3] * ld[1] + RE[r() * 3 + 1] * ld[2] + RE[r() * 3 + 2] * ld[3]);
+        });
+        ABRK_SCHED_FENCE();
+        get_w(w);
+        const T f[3] = {w[0], w[1], w[2]}, m[3] = {w[3], w[4], w[5]};
+        sfor<N>([&](auto i) ABRK_LAMBDA {
+          const T dl[3] = {pe[0] - jk.o[i()][0], pe[1] - jk.o[i()][1], pe[2] - jk.o[i()][2]};
+          T e[3];
+          wapply<i()>(jk, dl, e);
+          tau[i()] = Rm<T>::fma(c[F::ON_W], dot3(e, f) + dot3(jk.z[i()], m), tau[i()]);
+        });
+        ABRK_SCHED_FENCE();
+        // the payload: its point, Jp, the bias acceleration dJp dq (+ gravity), then -m Jp^T (...) and sqrt(m) Jp
+        const T sm = Rm<T>::sqrt(ld[0]);
+        T acc[3] = {T(0), T(0), gacc};
+        if constexpr (A::kOrtho) {
+          // dJp dq = sum_j dq_j (z_j x s_j + om_j x Jv_j) with s_j = sum_{k>=j} Jv_k dq_k and om_j = sum_{k<j} z_k dq_k
+          // (jacobian_dot), column by column from the last joint down: Jv_j is formed, parked and forgotten, and om_j
+          // comes off the total.  Held as arrays Jv and dJv - what jacobian() and jacobian_dot() return - cost the UR5
+          // fp64 kernel twelve registers beyond the two-wave budget (profiles/plant_step.md).
+          T om[3] = {T(0), T(0), T(0)}, sv3[3] = {T(0), T(0), T(0)};
+          sfor<N>([&](auto k) ABRK_LAMBDA {
+            sfor<3>([&](auto r) ABRK_LAMBDA { om[r()] = Rm<T>::fma(dq[k()], jk.z[k()][r()], om[r()]); });
+          });
+          sfor<N>([&](auto jr) ABRK_LAMBDA {
+            constexpr int j = N - 1 - jr();
+            const T dl[3] = {pp[0] - jk.o[j][0], pp[1] - jk.o[j][1], pp[2] - jk.o[j][2]};
+            T e[3], t1[3], t2[3];
+            cross3(jk.z[j], dl, e);
+            sfor<3>([&](auto r) ABRK_LAMBDA {
+              jpark.p[(j * 3 + r()) * jpark.stride] = sm * e[r()];
+              sv3[r()] = Rm<T>::fma(e[r()], dq[j], sv3[r()]);
+              om[r()] = Rm<T>::fma(-dq[j], jk.z[j][r()], om[r()]);
+            });
+            cross3(jk.z[j], sv3, t1);
+            cross3(om, e, t2);
+            sfor<3>([&](auto r) ABRK_LAMBDA { acc[r()] = Rm<T>::fma(dq[j], t1[r()] + t2[r()], acc[r()]); });
+            ABRK_SCHED_FENCE();
+          });
+        } else {
+          T Jv[N][3], Jw[N][3], dJv[N][3], dJw[N][3];
+          jacobian(jk, pp, N, Jv, Jw);
+          jacobian_dot(jk, dq, Jv, N, dJv, dJw);
+          sfor<N>([&](auto i) ABRK_LAMBDA {
+            sfor<3>([&](auto r) ABRK_LAMBDA {
+              acc[r()] = Rm<T>::fma(dJv[i()][r()], dq[i()], acc[r()]);
+              jpark.p[(i() * 3 + r()) * jpark.stride] = sm * Jv[i()][r()];
+            });
+          });
+        }
+        // -m Jp^T acc = -sqrt(m) (sqrt(m) Jp)^T acc, from the parked factor
+        const T* jp = reread(jpark.p);
+        sfor<N>([&](auto i) ABRK_LAMBDA {
+          const T col[3] = {jp[(i() * 3) * jpark.stride], jp[(i() * 3 + 1) * jpark.stride], jp[(i() * 3 + 2) * jpark.stride]};
+          tau[i()] = Rm<T>::fma(-sm, dot3(col, acc), tau[i()]);
+        });
+      }
+      {
+        const T* fr = reread(park.p);  // the friction torque, parked by phase C of the substep before
+        sfor<N>([&](auto i) ABRK_LAMBDA { tau[i()] += fr[i() * park.stride]; });
+      }
+      sfor<N>([&](auto i) ABRK_LAMBDA { park.p[i() * park.stride] = tau[i()]; });
+    }
+    ABRK_SCHED_FENCE();
+    // sin / cos for the dynamics pass, formed after phase A: nothing of theirs lives across it
+    T sv[N][2];
+    bool all_in = true;
+    sfor<N>([&](auto i) ABRK_LAMBDA {
+      if constexpr (std::remove_reference<Scr>::type::kHasTab) {
+        all_in = all_in && Rm<T>::sincos_tab_in_range(q[i()]);
+        Rm<T>::sincos_tab(q[i()], scr.sctab, sv[i()][0], sv[i()][1]);
+      } else {
+        all_in = all_in && Rm<T>::sincos_in_range(q[i()]);
+        Rm<T>::sincos_fast(q[i()], sv[i()][0], sv[i()][1]);
+      }
+    });
+    T svr[N][2];
+    sfor<N>([&](auto i) ABRK_LAMBDA {
+      svr[N - 1 - i()][1] = sv[i()][0];
+      svr[N - 1 - i()][0] = sv[i()][1];
+    });
+    if (!all_in)
+      sfor<N>([&](auto i) ABRK_LAMBDA {
+        const SinCosPair<T> r = sincos_out_of_line(q[i()]);
+        svr[N - 1 - i()][1] = r.s;
+        svr[N - 1 - i()][0] = r.c;
+      });
+    const ScUseRev<T, N> sincos_policy{svr};
+    // ---- B: the dynamics pass of plant_row
+    Joints<A, T> jt;
+    Dyn<A, T, REC ? CMODE_NONE : CMODE_VEC> d;
+    T XR[9], xo[3], cv2[REC ? N : 1];
+    if constexpr (REC) {
+      RneState<T> rne;
+      rne_init(rne);
+      kin_dyn_hook(arm, q, dq, jt, d, XR, xo, nc, [&](auto L, const T(&pl)[3]) ABRK_LAMBDA {
+        ABRK_SCHED_FENCE();
+        rne_forward_step<L()>(arm, jt, pl, dq, rne, scr);
+        ABRK_SCHED_FENCE();
+      }, sincos_policy);
+      rne_backward(jt, scr, cv2);
+    } else {
+      kin_dyn_hook(arm, q, dq, jt, d, XR, xo, nc, [](auto, const T(&)[3]) ABRK_LAMBDA {}, sincos_policy);
+    }
+    ABRK_SCHED_FENCE();
+    T rhs[N], y[N], tau[N];
+    {
+      const T* pp = reread(park.p);
+      sfor<N>([&](auto i) ABRK_LAMBDA { tau[i()] = pp[i() * park.stride]; });
+    }
+    sfor<N>([&](auto i) ABRK_LAMBDA {
+      if constexpr (REC) rhs[i()] = Rm<T>::fma(T(-1), cv2[i()], tau[i()]);
+      else rhs[i()] = Rm<T>::fma(T(-1), d.cv[i()], tau[i()]);
+    });
+    if (gravity) sfor<N>([&](auto i) ABRK_LAMBDA { rhs[i()] = Rm<T>::fma(T(9.81), d.gz[i()], rhs[i()]); });
+    // M + (sqrt(m) Jp)^T (sqrt(m) Jp): column i of the parked factor against columns j <= i
+    T Ma[N * (N + 1) / 2];
+    {
+      const T* jp = reread(jpark.p);
+      T P[N][3];
+      sfor<N>([&](auto i) ABRK_LAMBDA {
+        sfor<3>([&](auto r) ABRK_LAMBDA { P[i()][r()] = jp[(i() * 3 + r()) * jpark.stride]; });
+        sfor<i() + 1>([&](auto j) ABRK_LAMBDA { Ma[tri(i(), j())] = d.Ms[tri(i(), j())] + dot3(P[i()], P[j()]); });
+      });
+    }
+    T L[N * (N + 1) / 2], il[N];
+    chol<N, T, false>(Ma, L, il, &minpiv);
+    chol_fwd<N>(L, il, rhs, y);
+    chol_bwd<N>(L, il, y, ddq);
+    if (!integrate) break;
+    // ---- C: the update, then the limits
+    const T* c = reread(fxc);
+    const T bounce = -c[F::REST];
+    sfor<N>([&](auto i) ABRK_LAMBDA {
+      dq[i()] = Rm<T>::fma(ddq[i()], h, dq[i()]);
+      q[i()] = Rm<T>::fma(dq[i()], h, q[i()]);
+      const T lo = c[F::QMIN + i()], hi = c[F::QMAX + i()];
+      const bool out = ((int(q[i()] > hi) & int(dq[i()] > T(0))) | (int(q[i()] < lo) & int(dq[i()] < T(0)))) != 0;
+      q[i()] = Rm<T>::fmin(Rm<T>::fmax(q[i()], lo), hi);
+      dq[i()] = out ? bounce * dq[i()] : dq[i()];
+    });
+    park_friction(dq);
+  }
+}
+
 // ---------------------------------------------------------------- InverseKinematics.generate_path, one row
 // (controllers/path_planners/inverse_kinematics.py:84-135): n_steps sequential iterations, q in registers.
 template <class A, class T>

@@ -139,13 +139,35 @@ int check_plant_params(int arm_id, const abrk_plant_params* P) {
   if (P->substeps < 1) return fail(ABRK_EINVAL, "substeps=%d < 1", P->substeps);
   return 0;
 }
+// A host payload array [B, 4] = m, rx, ry, rz of `dtype`, looked at where it is about to be staged: m finite and >= 0, r
+// finite.  (A device array is taken as it is: the kernel reads it at every launch, long after any check here.)
+int check_payload_host(int dtype, int64_t B, const void* payload) {
+  for (int64_t b = 0; b < B; b++)
+    for (int k = 0; k < 4; k++) {
+      double v;
+      if (dtype == ABRK_F64) {
+        memcpy(&v, static_cast<const char*>(payload) + (b * 4 + k) * 8, 8);
+      } else {
+        float f;
+        memcpy(&f, static_cast<const char*>(payload) + (b * 4 + k) * 4, 4);
+        v = f;  // (exact; an infinity or a NaN stays one)
+      }
+      if (k == 0 ? !nonnegative_finite_at(&v) : !finite_at(&v))
+        return fail(ABRK_EINVAL, "payload: row %lld: %s=%g is not a finite value%s", (long long)b,
+                    k == 0 ? "m" : k == 1 ? "rx" : k == 2 ? "ry" : "rz", v, k == 0 ? " >= 0" : "");
+    }
+  return 0;
+}
 // mode 0: ddq out, q / dq read; mode 1: q / dq in place.  fx_entry: the entries with non-ideal effects, which launch the
-// effects kernel whatever is switched on; the others launch the plain kernel and pass no fx, tau_ext or wrench.
+// effects kernel whatever is switched on; the others launch the plain kernel and pass no fx, tau_ext or wrench.  With a
+// payload (fx entries only) the payload kernel is launched instead.
 int plant_impl(bool fx_entry, int arm_id, int dtype, int mode, double dt, int substeps, int gravity,
                const abrk_plant_effects* fx, int64_t B, void* q, void* dq, const void* u, const void* tau_ext,
-               const void* wrench, void* ddq, int device, void* stream) {
+               const void* wrench, void* ddq, int device, void* stream, const void* payload = nullptr) {
   ArmEntry* a;
   if (int rc = check_common(arm_id, dtype, B, &a)) return rc;
+  if (payload && !a->ops->plant_load)
+    return fail(ABRK_EINVAL, "this arm's kernels carry no plant with a payload (rebuild its plugin)");
   if (!fx_entry && !a->ops->plant) return fail(ABRK_EINVAL, "this arm's kernels carry no plant (rebuild its plugin)");
   if (fx_entry && !a->ops->plant_fx)
     return fail(ABRK_EINVAL, "this arm's kernels carry no plant with effects (rebuild its plugin)");
@@ -153,9 +175,12 @@ int plant_impl(bool fx_entry, int arm_id, int dtype, int mode, double dt, int su
   const int n = a->desc.n_joints;
   if (int rc = check_effects(fx, n)) return rc;
   if (B == 0) return 0;
+  if (payload && !device_view(payload))
+    if (int rc = check_payload_host(dtype, B, payload)) return rc;
   if (int rc = use_device(device)) return rc;
   const size_t bytes = (size_t)B * n * esz(dtype);
   Stager st{device, (hipStream_t)stream};
+  const void* pl = nullptr;
   PlantFxArgs pa{};  // (the plain kernel's PlantArgs: its q, dq, u and ddq)
   if (mode == 0) {
     st.bind(&pa.q, q, bytes, true, false);
@@ -167,6 +192,7 @@ int plant_impl(bool fx_entry, int arm_id, int dtype, int mode, double dt, int su
   st.in(&pa.u, u, bytes);
   st.in(&pa.tau_ext, tau_ext, bytes);
   st.in(&pa.wrench, wrench, (size_t)B * 6 * esz(dtype));
+  st.in(&pl, payload, (size_t)B * 4 * esz(dtype));
   st.out(&pa.ddq, mode == 0 ? ddq : nullptr, bytes);
   if (int rc = st.reserve()) return rc;
   auto pb = blocks([&](auto t) { return make_plantp<decltype(t)>(dt / substeps, substeps, gravity, mode); });
@@ -182,6 +208,7 @@ int plant_impl(bool fx_entry, int arm_id, int dtype, int mode, double dt, int su
       PlantFxArgs o = pa;
       o.P = pb.of(dtype);
       o.F = fb.of(dtype);
+      if (payload) return ops->plant_load(dtype, LaunchArgs{rt, (long)B, hs}, PlantLoadArgs{o, pl});
       return ops->plant_fx(dtype, LaunchArgs{rt, (long)B, hs}, o);
     });
   });
@@ -214,6 +241,23 @@ extern "C" int abrk_plant_step_fx_batch(int arm_id, int dtype, const abrk_plant_
   if (int rc = check_plant_params(arm_id, P)) return rc;
   return plant_impl(true, arm_id, dtype, 1, P->dt, P->substeps, P->gravity ? 1 : 0, fx, B, q, dq, u, tau_ext, wrench,
                     nullptr, device, stream);
+}
+
+extern "C" int abrk_forward_dynamics_payload_batch(int arm_id, int dtype, const abrk_plant_effects* fx, int64_t B,
+                                                   const void* q, const void* dq, const void* u, const void* tau_ext,
+                                                   const void* wrench, const void* payload, void* ddq, int device,
+                                                   void* stream) {
+  return plant_impl(true, arm_id, dtype, 0, 1.0, 1, 1, fx, B, const_cast<void*>(q), const_cast<void*>(dq), u, tau_ext,
+                    wrench, ddq, device, stream, payload);
+}
+
+extern "C" int abrk_plant_step_payload_batch(int arm_id, int dtype, const abrk_plant_params* P,
+                                             const abrk_plant_effects* fx, int64_t B, void* q, void* dq, const void* u,
+                                             const void* tau_ext, const void* wrench, const void* payload, int device,
+                                             void* stream) {
+  if (int rc = check_plant_params(arm_id, P)) return rc;
+  return plant_impl(true, arm_id, dtype, 1, P->dt, P->substeps, P->gravity ? 1 : 0, fx, B, q, dq, u, tau_ext, wrench,
+                    nullptr, device, stream, payload);
 }
 
 // ------------------------------------------------------------------------------- loop recorder

@@ -518,6 +518,35 @@ plant_fx_kernel(A arm, PlantP<T> P, PlantFxP<T> F, long B, T* __restrict__ qg, T
   plant_fx_body<A, T>(b, arm, P, fxc, qg, dqg, ug, extg, wg, ddqg, park, scr);
 }
 
+// The plant with a payload at the end effector (abrk_ctrl.h plant_load_row): a third kernel beside the two above, one
+// instantiation per (arm, type).  plant_fx_kernel's LDS plus 3 N values per lane where sqrt(m) Jp waits for the dynamics
+// pass (9 KiB for a six-joint fp64 arm).  `pg` [B, 4] is read by ordinary per-lane loads at every launch.
+template <class A, class T>
+__global__ void __launch_bounds__(kBlock, osc_min_waves(3, true, 0, osc_ortho<A>(), 0, A::kStatic))
+plant_load_kernel(A arm, PlantP<T> P, PlantFxP<T> F, long B, T* __restrict__ qg, T* __restrict__ dqg,
+                  const T* __restrict__ ug, const T* __restrict__ extg, const T* __restrict__ wg,
+                  const T* __restrict__ pg, T* __restrict__ ddqg) {
+  constexpr bool kLds = plant_uses_slab<A>();
+  using V2 = typename LdsScratch<T, A::N>::V2;
+  __shared__ T sctab[2 * kSinCosN];
+  __shared__ T fxc[PlantFxP<T>::COUNT];
+  for (int k = 0; k < PlantFxP<T>::COUNT; k++) fxc[k] = F.c[k];
+  load_sincos_table(sctab, (int)threadIdx.x);  // every lane takes part: before any exit (it ends with the barrier)
+  __shared__ V2 slab[kLds ? 3 * A::N * kBlock : 1];
+  ABRK_ROW_INDEX
+  std::conditional_t<kLds, LdsScratch<T, A::N>, TabScratch<T, A::N>> scr;
+  if constexpr (kLds) {
+    scr.slab = slab;
+    scr.lane = (int)threadIdx.x;
+  }
+  scr.sctab = sctab;
+  __shared__ T taus[A::N * kBlock];      // [N][kBlock]
+  __shared__ T jps[3 * A::N * kBlock];   // [3 N][kBlock]: a lane's values kBlock apart, no bank conflict
+  const FxPark<T> park{taus + threadIdx.x, kBlock};
+  const FxPark<T> jpark{jps + threadIdx.x, kBlock};
+  plant_load_body<A, T>(b, arm, P, fxc, qg, dqg, ug, extg, wg, pg, ddqg, park, jpark, scr);
+}
+
 // The loop recorder (abrk_trace.h trace_body): forward kinematics only, so two waves per SIMD without scratch.
 // History rows of a wavefront whose rows share one slot - every wavefront, until a caller restarts some rows on their
 // own - are parked in LDS laid out like the slot's 64-row block of the history and streamed out linearly: 16 bytes per
@@ -750,6 +779,10 @@ struct PlantFxArgs {
   const void *u, *tau_ext, *wrench;  // tau_ext [B, N] and wrench [B, 6] may be null
   void* ddq;
 };
+struct PlantLoadArgs {
+  PlantFxArgs fx;       // as the effects kernel
+  const void* payload;  // [B, 4]: m, rx, ry, rz
+};
 struct TraceArgs {
   const void* P;  // TraceP<T>
   const void *q, *dq, *u, *target;
@@ -807,6 +840,7 @@ struct ArmOps {
   hipError_t (*plant)(int dtype, const LaunchArgs&, const PlantArgs&);
   hipError_t (*trace)(int dtype, const LaunchArgs&, const TraceArgs&);
   hipError_t (*plant_fx)(int dtype, const LaunchArgs&, const PlantFxArgs&);
+  hipError_t (*plant_load)(int dtype, const LaunchArgs&, const PlantLoadArgs&);
 };
 hipError_t launch_twolink_step(int dtype, const LaunchArgs& la, const void* K, void* q, void* dq, const void* u);
 
@@ -920,6 +954,13 @@ struct Launch {
                        (T*)a.dq, (const T*)a.u, (const T*)a.tau_ext, (const T*)a.wrench, (T*)a.ddq);
     return hipGetLastError();
   }
+  static hipError_t plant_load(const LaunchArgs& la, const PlantLoadArgs& l) {
+    const PlantFxArgs& a = l.fx;
+    hipLaunchKernelGGL((plant_load_kernel<A, T>), grid_for(la.B), dim3(kBlock), 0, la.stream, arm_of(la),
+                       *static_cast<const PlantP<T>*>(a.P), *static_cast<const PlantFxP<T>*>(a.F), la.B, (T*)a.q,
+                       (T*)a.dq, (const T*)a.u, (const T*)a.tau_ext, (const T*)a.wrench, (const T*)l.payload, (T*)a.ddq);
+    return hipGetLastError();
+  }
   static hipError_t trace(const LaunchArgs& la, const TraceArgs& a) {
     // measurement switch: the row-per-lane history stores for every wavefront (profiles/loop_trace.md)
     static const bool plain = measurement_env("ABRK_TRACE_PLAIN") != nullptr;
@@ -992,7 +1033,8 @@ struct OpsFor {
                              &by_dtype<&LD::obstacles, &LF::obstacles>,
                              &by_dtype<&LD::plant, &LF::plant>,
                              &by_dtype<&LD::trace, &LF::trace>,
-                             &by_dtype<&LD::plant_fx, &LF::plant_fx>};
+                             &by_dtype<&LD::plant_fx, &LF::plant_fx>,
+                             &by_dtype<&LD::plant_load, &LF::plant_load>};
     return &o;
   }
 };

@@ -581,6 +581,44 @@ ABRK_INL void plant_fx_body(long b, const A& arm, const PlantP<T>& P, const T* f
   if (any_lane(!(minpiv > T(0))) && P.status) *P.status = 1;
 }
 
+// ---- the plant with a payload at the end effector (abrk_ctrl.h plant_load_row): plant_fx_body plus `pg` [B, 4] = m, rx,
+// ry, rz per row, never null (the host forwards a call without a payload to the effects entry).  Read per lane, with
+// ordinary loads, where a substep consumes it - so a recorded plan sees a mass rewritten between replays.
+template <class A, class T, class Scr>
+ABRK_INL void plant_load_body(long b, const A& arm, const PlantP<T>& P, const T* fxc, T* __restrict__ qg,
+                              T* __restrict__ dqg, const T* __restrict__ ug, const T* __restrict__ extg,
+                              const T* __restrict__ wg, const T* __restrict__ pg, T* __restrict__ ddqg,
+                              const FxPark<T>& park, const FxPark<T>& jpark, Scr& scr) {
+  constexpr int N = A::N;
+  T q[N], dq[N], ddq[N];
+  load_row<N>(qg, b, q);
+  load_row<N>(dqg, b, dq);
+  auto row = [&]() ABRK_LAMBDA {
+    long bb = b;
+    opaque(bb);
+    return bb;
+  };
+  auto get_u = [&](T(&u)[N]) ABRK_LAMBDA { load_row<N>(ug, row(), u); };
+  auto get_ext = [&](T(&e)[N]) ABRK_LAMBDA { load_row<N>(extg ? extg : ug, row(), e); };
+  auto get_w = [&](T(&w)[6]) ABRK_LAMBDA {
+    const T* wp = wg ? wg + row() * 6 : ug + row() * N;
+    const int step = wg ? 1 : 0;
+    sfor<6>([&](auto k) ABRK_LAMBDA { w[k()] = wp[k() * step]; });
+  };
+  auto get_load = [&](T(&l)[4]) ABRK_LAMBDA { load_row<4>(pg, row(), l); };
+  T minpiv = T(1);
+  const bool integrate = P.mode != 0;
+  plant_load_row<A, T>(arm, P.h, integrate ? P.substeps : 1, P.gravity != 0, integrate, fxc, q, dq, get_u, get_ext, get_w,
+                       get_load, park, jpark, ddq, minpiv, scr);
+  if (integrate) {
+    store_row<N>(qg, row(), q);
+    store_row<N>(dqg, row(), dq);
+  } else {
+    store_row<N>(ddqg, row(), ddq);
+  }
+  if (any_lane(!(minpiv > T(0))) && P.status) *P.status = 1;
+}
+
 // ---- OSC._Mx / ._velocity_limiting / ._calc_orientation_forces for B rows (osc.py:120-215)
 template <int N, class T>
 ABRK_INL void mx_body(long b, int k, T thr, const T* __restrict__ Mg, const T* __restrict__ Jg, T* __restrict__ Mxg,

@@ -402,6 +402,28 @@ int abrk_plant_step_fx_batch(int arm_id, int dtype, const abrk_plant_params* par
                              int device, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * The same plant carrying a payload that differs from row to row: a point mass m[b] >= 0 fixed to the end-effector
+ * link at offset r[b] from the origin of the EE frame, in that frame's coordinates (the x of
+ * robot_config.Tx("EE", q, x=r)).  Row b is the arm with one more link of _M_LINKS = diag(m, m, m, 0, 0, 0) whose centre
+ * of mass is that point.  `payload` is [B,4] of `dtype`: m, rx, ry, rz.  With Jp = J("EE", q, x=r)[:3] and
+ * dJp = dJ("EE", q, dq, x=r)[:3], step 3 of the sequence above becomes
+ *   ddq = (M + m Jp^T Jp)^-1 (tau - C dq - m Jp^T (dJp dq) - g - Jp^T m (0, 0, -9.81)^T)
+ * (gravity = 0 leaves both gravity terms out); steps 1, 2, 4 and 5 are unchanged, q and dq are those of the substep's
+ * start, and ABRK_ESINGULAR looks at the pivots of the augmented matrix.  The payload has no rotational inertia.
+ * fx, tau_ext and wrench stay optional.  payload == NULL forwards to the *_fx entry point: the same bits.
+ * A HOST payload array is validated before it is staged: a negative or non-finite m, or a non-finite r, is
+ * ABRK_EINVAL with the row in the message.  A DEVICE array is NOT validated: the kernel reads it with ordinary
+ * per-lane loads at every launch, so a recorded plan picks up a mass rewritten between replays, and what a bad value
+ * does there is the caller's business (a negative m can make the augmented matrix indefinite: ABRK_ESINGULAR or NaN).
+ * --------------------------------------------------------------------------------- */
+int abrk_forward_dynamics_payload_batch(int arm_id, int dtype, const abrk_plant_effects* fx, int64_t B, const void* q,
+                                        const void* dq, const void* u, const void* tau_ext, const void* wrench,
+                                        const void* payload, void* ddq, int device, void* stream);
+int abrk_plant_step_payload_batch(int arm_id, int dtype, const abrk_plant_params* params, const abrk_plant_effects* fx,
+                                  int64_t B, void* q, void* dq, const void* u, const void* tau_ext, const void* wrench,
+                                  const void* payload, int device, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Iterative inverse kinematics: InverseKinematics.generate_path
  * (abr_control/controllers/path_planners/inverse_kinematics.py:28-135) for B independent paths, all
  * n_timesteps iterations of a path inside one kernel (each iteration: Tx, J, quaternion of the EE, two

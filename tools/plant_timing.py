@@ -15,6 +15,12 @@ five rounds of 12 warm-up + 30 timed launches each; the figure is the median ove
 plain step of the same rounds.  Prints ONE JSON line.
 
     python tools/plant_timing.py --effects [--rows-fx 1048576]
+
+--payload: the same leg with the payload step beside them (profiles/plant_step.md): plain entry point, effects entry
+point with everything on, payload entry point with nothing else, and with everything on; payloads of 0.2 - 3 kg within
+10 cm of the end effector, every seventh row without a mass.  Same rounds, same table form, ratios to the plain step.
+
+    python tools/plant_timing.py --payload [--rows-fx 1048576]
 """
 import argparse
 import json
@@ -28,14 +34,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 WARMUP, TIMED = 12, 30
 
 
-def effects_leg(rows_large):
+def effects_leg(rows_large, payload=False):
     import abr_control_amd as a
-    from abr_control_amd import _abi, engine
+    from abr_control_amd import _abi, engine, plant_payload
     from abr_control_amd.arms import jaco2, ur5
 
     s = a.Stream(0)
     p = _abi.make_plant_params(1e-3)
-    res = {"leg": "effects", "dtype": "float64", "device": a.device_name(0), "warmup": WARMUP, "timed": TIMED,
+    res = {"leg": "payload" if payload else "effects", "dtype": "float64", "device": a.device_name(0), "warmup": WARMUP, "timed": TIMED,
            "rounds": 5, "us": {}}
     e0, e1 = a.Event(0), a.Event(0)
 
@@ -64,6 +70,9 @@ def effects_leg(rows_large):
             u, ext, w = (a.DeviceArray.from_numpy(x) for x in (rng.uniform(-20, 20, (B, n)), rng.uniform(-5, 5, (B, n)),
                                                                rng.uniform(-10, 10, (B, 6))))
             q, dq = a.DeviceArray.from_numpy(q0), a.DeviceArray.from_numpy(dq0)
+            load = np.concatenate([rng.uniform(0.2, 3.0, (B, 1)), rng.uniform(-0.1, 0.1, (B, 3))], axis=1)
+            load[::7, 0] = 0
+            pl = a.DeviceArray.from_numpy(load) if payload else None
 
             def reset():  # every round starts from the same state: the three forms see the same rows
                 q.copy_from_numpy(q0, stream=s)
@@ -76,6 +85,16 @@ def effects_leg(rows_large):
                 "fx_all_on": lambda: engine.plant_step(rc.arm_id, n, p, q, dq, u, stream=s, effects=all_on, tau_ext=ext,
                                                        wrench=w),
             }
+            if payload:
+                forms = {
+                    "plain": forms["plain"],
+                    "fx_all_on": forms["fx_all_on"],
+                    "payload_alone": lambda: plant_payload.plant_step(rc.arm_id, n, p, q, dq, u, stream=s,
+                                                                      payload=pl),
+                    "payload_all_on": lambda: plant_payload.plant_step(rc.arm_id, n, p, q, dq, u, stream=s,
+                                                                       effects=all_on, tau_ext=ext, wrench=w,
+                                                                       payload=pl),
+                }
             ts = {k: [] for k in forms}
             for _ in range(res["rounds"]):
                 for k, fn in forms.items():
@@ -83,7 +102,9 @@ def effects_leg(rows_large):
                     ts[k] += one_round(fn)
             out = {k: {"median_us": float(np.median(v)), "min_us": float(np.min(v)), "max_us": float(np.max(v))}
                    for k, v in ts.items()}
-            for k in ("fx_all_off", "fx_all_on"):
+            for k in forms:
+                if k == "plain":
+                    continue
                 out[k]["ratio_to_plain"] = out[k]["median_us"] / out["plain"]["median_us"]
             res["us"][name][str(B)] = out
     print(json.dumps(res))
@@ -93,10 +114,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows-large", type=int, default=8 << 20)
     ap.add_argument("--effects", action="store_true", help="time the plant with effects against the plain step")
+    ap.add_argument("--payload", action="store_true", help="time the payload step against the effects and the plain step")
     ap.add_argument("--rows-fx", type=int, default=1 << 20)
     args = ap.parse_args()
-    if args.effects:
-        return effects_leg(args.rows_fx)
+    if args.effects or args.payload:
+        return effects_leg(args.rows_fx, payload=args.payload)
     import abr_control_amd as a
     from abr_control_amd import _abi, engine
     from abr_control_amd.arms import ur5
