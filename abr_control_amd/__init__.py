@@ -7,6 +7,7 @@ controllers; both evaluate one state or a batch of states with hand-written HIP 
 """
 from . import arms, controllers  # noqa: F401
 from ._lib import AbrkError, DeviceArray, Event, Stream, device_count, device_name, scratch_stats  # noqa: F401
+from .contact import ContactSurfaces  # noqa: F401
 from .recorder import LoopRecorder  # noqa: F401
 from .sensing import JointSensor, SignalChannel  # noqa: F401
 

@@ -346,6 +346,34 @@ def make_trace_params(frame, x_off=None, every=1, capacity=0, columns=("xyz", "e
     return p
 
 
+CONTACT_MAX_SURFACES = 4  # ABRK_CONTACT_MAX_SURFACES (include/abrk.h)
+CONTACT_SURFACE = ("nx", "ny", "nz", "d", "k", "c", "mu", "rho")  # the columns of surface [B,S,8]
+
+
+class ContactParams(C.Structure):
+    """abrk_contact_params (include/abrk.h)"""
+    _fields_ = [("frame", C.c_int32), ("off", C.c_double * 3), ("n_surfaces", C.c_int32), ("vs", C.c_double),
+                ("accumulate", C.c_int32)]
+
+
+def make_contact_params(n, frame="EE", offset=(0, 0, 0), n_surfaces=1, vs=1e-3, accumulate=False):
+    """Parameters of contact.contact_step for an arm of `n` joints: `frame` a name robot_config.Tx accepts ("EE",
+    "link{i}", "joint{i}") or the number frame_id() gives it, `offset` the tool offset in that frame, `n_surfaces` the
+    half-spaces per row (1..4), `vs` the smoothing speed of the friction law (m/s), `accumulate`: tau += instead of
+    tau =.  The values are checked by the C entry point."""
+    p = ContactParams()
+    p.frame = int(frame) if isinstance(frame, (int, np.integer)) else frame_id(frame, int(n))
+    off = np.asarray(offset, dtype=float)
+    if off.shape != (3,):
+        raise ValueError(f"offset has shape {off.shape}; expected (3,)")
+    for r in range(3):
+        p.off[r] = off[r]
+    p.n_surfaces = int(n_surfaces)
+    p.vs = float(vs)
+    p.accumulate = int(bool(accumulate))
+    return p
+
+
 ADAPT_LIF, ADAPT_LIF_RATE = 0, 1  # ABRK_ADAPT_* (include/abrk.h)
 ADAPT_NEURON_TYPES = {"lif": ADAPT_LIF, "lif_rate": ADAPT_LIF_RATE}
 ADAPT_MAX_INPUT, ADAPT_MAX_OUTPUT = 64, 16

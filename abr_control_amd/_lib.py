@@ -114,6 +114,8 @@ def lib():
         L.abrk_path_next_batch.argtypes = [C.c_int, _i64, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]
         L.abrk_loop_trace_batch.argtypes = [C.c_int, C.c_int, C.POINTER(_abi.TraceParams), _i64] + [_vp] * 8 + [
             C.c_int, _vp]
+        L.abrk_contact_step_batch.argtypes = [C.c_int, C.c_int, C.POINTER(_abi.ContactParams), _i64] + [_vp] * 5 + [
+            C.c_int, _vp]
         L.abrk_adapt_step_batch.argtypes = [C.c_int, C.POINTER(_abi.AdaptParams), _i64] + [_vp] * 6 + [
             C.c_int32, _vp, C.c_int32, _vp, C.POINTER(_abi.AdaptState), _vp, _vp, C.c_int, _vp]
         L.abrk_channel_step_batch.argtypes = [C.c_int, C.POINTER(_abi.ChannelParams), _i64, _vp, C.c_int32, _vp,

@@ -6,14 +6,17 @@ dt / 1e-5 such substeps).  `effects` (_abi.make_plant_effects) makes the plant n
 smoothed Coulomb joint friction, hard joint limits with restitution; send_forces also takes a joint-space disturbance
 `tau_ext` and a world-frame wrench at the end effector (include/abrk.h, abrk_plant_effects).  `payload` is a point mass
 carried at the end effector - (m, r) for every arm, or [B, 4] rows of m, rx, ry, rz - which changes M, C and g of the
-plant and which the robot_config (the controller's model) knows nothing of.  No contacts."""
+plant and which the robot_config (the controller's model) knows nothing of.  `surfaces` are planes the arm can touch: a
+contact.ContactSurfaces, or planes [S, 8] / [B, S, 8] of nx, ny, nz, d, k, c, mu, rho for a tip at the origin of the
+end-effector frame; the contact torque of the state at the start of a step is added to that step's tau_ext."""
 import numpy as np
 
-from .. import _abi, engine, plant_payload
+from .. import _abi, contact, engine, plant_payload
 
 
 class ArmSim:
-    def __init__(self, robot_config, dt=0.001, q_init=None, substeps=1, gravity=True, effects=None, payload=None):
+    def __init__(self, robot_config, dt=0.001, q_init=None, substeps=1, gravity=True, effects=None, payload=None,
+                 surfaces=None):
         self.robot_config = robot_config
         n = robot_config.N_JOINTS
         q0 = q_init if q_init is not None else getattr(robot_config, "START_ANGLES", None)
@@ -25,6 +28,8 @@ class ArmSim:
         self.gravity = bool(gravity)
         self.effects = effects
         self.payload = self._payload_rows(payload)
+        self.surfaces = surfaces
+        self._contact_report = None
         self.t = 0.0
         self.reset()
 
@@ -48,6 +53,24 @@ class ArmSim:
         """the payload carried from the next step on: None, (m, r), (4,) or (B, 4) of m, rx, ry, rz"""
         self.payload = self._payload_rows(payload)
 
+    def _contact(self, q, dq, dtype):
+        """-> the contact torque [B, n] of the state (q, dq) on self.surfaces; keeps the report"""
+        rc, B = self.robot_config, q.shape[0]
+        sf = self.surfaces
+        if isinstance(sf, contact.ContactSurfaces):
+            planes, params = contact.planes_rows(sf.planes, B), sf.params()
+        else:
+            planes = contact.planes_rows(sf, B)
+            params = _abi.make_contact_params(rc.N_JOINTS, n_surfaces=planes.shape[1])
+        tau, self._contact_report = contact.contact_step(rc.arm_id, rc.N_JOINTS, params, q, dq, planes.astype(dtype),
+                                                         None, report=True, dtype=dtype, device=rc.device)
+        return tau
+
+    def contact_report(self):
+        """the report of the last send_forces: {"force", "force_local", "depth", "n_contacts"} (contact.report_dict), one
+        row per arm; None before the first step or without surfaces"""
+        return None if self._contact_report is None else contact.report_dict(self._contact_report)
+
     def connect(self):
         self.reset()
 
@@ -63,7 +86,8 @@ class ArmSim:
 
     def send_forces(self, u, dt=None, tau_ext=None, wrench=None):
         """advance one time step under torques u (arm_sim.py:67-82); tau_ext (n,) or (B, n) and wrench (6,) or (B, 6) are
-        loads the controller does not know of; the payload carried is self.payload (set_payload changes it between steps)"""
+        loads the controller does not know of; the payload carried is self.payload (set_payload changes it between steps);
+        with surfaces the contact is evaluated first and its torque added to tau_ext"""
         rc = self.robot_config
         dtype = np.dtype(getattr(rc, "dtype", np.float64))
         single = self.q.ndim == 1
@@ -77,8 +101,12 @@ class ArmSim:
                 return None
             return np.ascontiguousarray(np.broadcast_to(np.atleast_2d(np.asarray(x, dtype=dtype)), (q.shape[0], w)))
 
+        ext = rows(tau_ext, q.shape[1])
+        if self.surfaces is not None:
+            tau_c = self._contact(q, dq, dtype)
+            ext = tau_c if ext is None else ext + tau_c
         plant_payload.plant_step(rc.arm_id, rc.N_JOINTS, params, q, dq, u2, dtype=dtype, device=rc.device,
-                                 effects=self.effects, tau_ext=rows(tau_ext, q.shape[1]), wrench=rows(wrench, 6),
+                                 effects=self.effects, tau_ext=ext, wrench=rows(wrench, 6),
                                  payload=rows(self.payload, 4))
         self.q, self.dq = (q[0], dq[0]) if single else (q, dq)
         self.t += self.dt

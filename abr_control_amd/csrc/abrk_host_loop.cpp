@@ -1,5 +1,7 @@
 // abrk_host_loop.cpp - what a closed loop adds around the law: two-link step and rollout, the rigid-body plant, the
-// loop recorder, the path planner, the adaptive signal and the measurement channel.
+// loop recorder, end-effector contact, the path planner, the adaptive signal and the measurement channel.
+#include <cmath>
+
 #include "abrk_host.h"
 #include "abrk_adapt.h"
 #include "abrk_channel.h"
@@ -327,6 +329,83 @@ extern "C" int abrk_loop_trace_batch(int arm_id, int dtype, const abrk_trace_par
   Pc.columns = cols;
   const auto pb = blocks([&](auto t) { return make_tracep<decltype(t)>(Pc, n); });
   return launch_arm(st, a, dtype, B, &ArmOps::trace, ta, pb);
+}
+
+// ------------------------------------------------------------------------------- end-effector contact
+namespace {
+static_assert(ABRK_CONTACT_MAX_SURFACES == kContactMaxSurfaces, "abrk.h and abrk_contact.h agree on the surfaces of a row");
+template <class T>
+ContactP<T> make_contactp(const abrk_contact_params& P, int n) {
+  ContactP<T> p;
+  p.frame = P.frame;
+  p.m = frame_m(P.frame, n);
+  for (int r = 0; r < 3; r++) p.off[r] = T(P.off[r]);
+  p.S = P.n_surfaces;
+  p.vs2 = T(P.vs * P.vs);
+  p.accumulate = P.accumulate ? 1 : 0;
+  return p;
+}
+// A host surface array [B, S, 8] = nx, ny, nz, d, k, c, mu, rho of `dtype`, looked at where it is about to be staged:
+// everything finite, | |n| - 1 | <= 1e-6, and k, c, mu, rho >= 0.  (A device array is taken as it is.)
+int check_surface_host(int dtype, int64_t B, int S, const void* surface) {
+  static const char* const names[8] = {"nx", "ny", "nz", "d", "k", "c", "mu", "rho"};
+  for (int64_t b = 0; b < B; b++)
+    for (int s = 0; s < S; s++) {
+      double v[8];
+      for (int k = 0; k < 8; k++) {
+        const int64_t at = (b * S + s) * 8 + k;
+        if (dtype == ABRK_F64) {
+          memcpy(&v[k], static_cast<const char*>(surface) + at * 8, 8);
+        } else {
+          float f;
+          memcpy(&f, static_cast<const char*>(surface) + at * 4, 4);
+          v[k] = f;  // (exact; an infinity or a NaN stays one)
+        }
+        if (!finite_at(&v[k]))
+          return fail(ABRK_EINVAL, "surface: row %lld, surface %d: %s is not finite", (long long)b, s, names[k]);
+        if (k >= 4 && !nonnegative_finite_at(&v[k]))
+          return fail(ABRK_EINVAL, "surface: row %lld, surface %d: %s=%g is negative", (long long)b, s, names[k], v[k]);
+      }
+      const double len = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+      if (!(std::fabs(len - 1.0) <= 1e-6))
+        return fail(ABRK_EINVAL, "surface: row %lld, surface %d: |n|=%.9g is not 1 to within 1e-6", (long long)b, s, len);
+    }
+  return 0;
+}
+}  // namespace
+
+extern "C" int abrk_contact_step_batch(int arm_id, int dtype, const abrk_contact_params* P, int64_t B, const void* q,
+                                       const void* dq, const void* surface, void* tau, void* report, int device,
+                                       void* stream) {
+  ArmEntry* a;
+  if (int rc = check_common(arm_id, dtype, B, &a)) return rc;
+  if (!a->ops->contact) return fail(ABRK_EINVAL, "this arm's kernels carry no contact step (rebuild its plugin)");
+  if (!P) return fail(ABRK_EINVAL, "params is NULL");
+  const int n = a->desc.n_joints;
+  if (P->frame < 0 || P->frame > 2 * n + 1) return fail(ABRK_EINVAL, "Invalid transformation name: frame id %d", P->frame);
+  for (int r = 0; r < 3; r++)
+    if (!finite_at(&P->off[r])) return fail(ABRK_EINVAL, "off[%d] is not finite", r);
+  if (P->n_surfaces < 1 || P->n_surfaces > ABRK_CONTACT_MAX_SURFACES)
+    return fail(ABRK_EINVAL, "n_surfaces=%d outside 1..%d", P->n_surfaces, ABRK_CONTACT_MAX_SURFACES);
+  if (!positive_finite_at(&P->vs)) return fail(ABRK_EINVAL, "vs=%g is not a finite value > 0", P->vs);
+  if (!q || !dq || !surface || !tau) return fail(ABRK_EINVAL, "q, dq, surface and tau are required");
+  if (B == 0) return 0;
+  const int S = P->n_surfaces;
+  if (!device_view(surface))
+    if (int rc = check_surface_host(dtype, B, S, surface)) return rc;
+  if (int rc = use_device(device)) return rc;
+  const size_t s = esz(dtype);
+  Stager st{device, (hipStream_t)stream};
+  ContactArgs ca{};
+  st.in(&ca.q, q, (size_t)B * n * s);
+  st.in(&ca.dq, dq, (size_t)B * n * s);
+  st.in(&ca.surface, surface, (size_t)B * S * 8 * s);
+  // (accumulate: tau goes in as well as out)
+  st.bind(&ca.tau, tau, (size_t)B * n * s, P->accumulate != 0, true);
+  st.out(&ca.report, report, (size_t)B * 8 * s);
+  if (int rc = st.reserve()) return rc;
+  const auto pb = blocks([&](auto t) { return make_contactp<decltype(t)>(*P, n); });
+  return launch_arm(st, a, dtype, B, &ArmOps::contact, ca, pb);
 }
 
 // ------------------------------------------------------------------------------- path planner

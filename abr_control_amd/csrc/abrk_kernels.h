@@ -8,6 +8,7 @@
 #include "abrk_rows.h"
 #include "abrk_select.h"
 #include "abrk_trace.h"
+#include "abrk_contact.h"
 
 namespace abrk {
 
@@ -598,6 +599,16 @@ trace_kernel(A arm, TraceP<T> P, long B, TraceIO<T> io) {
   trace_body<A, T>(b, b < B, st, arm, P, B, io);
 }
 
+// End-effector contact (abrk_contact.h contact_body): forward kinematics and the point Jacobian, one lane per row, so
+// two waves per SIMD without scratch like the recorder.  No LDS: a row's S * 8 surface values are contiguous, so every
+// lane reads whole 32- or 64-byte runs and the wavefront's lines are used in full (profiles/contact_step.md).
+template <class A, class T>
+__global__ void __launch_bounds__(kBlock, 2)
+contact_kernel(A arm, ContactP<T> P, long B, ContactIO<T> io) {
+  ABRK_ROW_INDEX
+  contact_body<A, T>(b, arm, P, io);
+}
+
 template <class A, class T>
 __global__ void __launch_bounds__(kBlock, kMinWaves)
 ik_kernel(A arm, IkP<T> P, long B, const T* __restrict__ qg, const T* __restrict__ tg, T* __restrict__ pp,
@@ -788,6 +799,11 @@ struct TraceArgs {
   const void *q, *dq, *u, *target;
   void *counter, *history, *stats, *settle;
 };
+struct ContactArgs {
+  const void* P;  // ContactP<T>
+  const void *q, *dq, *surface;
+  void *tau, *report;  // report may be null
+};
 struct LawArgs {
   const void* P;  // OscP<T>
   const void *J, *M, *g, *c, *xyz, *R, *q, *dq, *target, *tv, *une;
@@ -841,6 +857,7 @@ struct ArmOps {
   hipError_t (*trace)(int dtype, const LaunchArgs&, const TraceArgs&);
   hipError_t (*plant_fx)(int dtype, const LaunchArgs&, const PlantFxArgs&);
   hipError_t (*plant_load)(int dtype, const LaunchArgs&, const PlantLoadArgs&);
+  hipError_t (*contact)(int dtype, const LaunchArgs&, const ContactArgs&);
 };
 hipError_t launch_twolink_step(int dtype, const LaunchArgs& la, const void* K, void* q, void* dq, const void* u);
 
@@ -971,6 +988,12 @@ struct Launch {
     hipLaunchKernelGGL((trace_kernel<A, T>), grid_for(la.B), dim3(kBlock), 0, la.stream, arm_of(la), P, la.B, io);
     return hipGetLastError();
   }
+  static hipError_t contact(const LaunchArgs& la, const ContactArgs& a) {
+    const ContactIO<T> io{(const T*)a.q, (const T*)a.dq, (const T*)a.surface, (T*)a.tau, (T*)a.report};
+    hipLaunchKernelGGL((contact_kernel<A, T>), grid_for(la.B), dim3(kBlock), 0, la.stream, arm_of(la),
+                       *static_cast<const ContactP<T>*>(a.P), la.B, io);
+    return hipGetLastError();
+  }
   static hipError_t rollout(const LaunchArgs& la, const RolloutArgs& a) {
     if constexpr (A::N == 2) {
       with_rollout_variant(a.fast, a.use_C != 0, [&](auto uc, auto km) {
@@ -1034,7 +1057,8 @@ struct OpsFor {
                              &by_dtype<&LD::plant, &LF::plant>,
                              &by_dtype<&LD::trace, &LF::trace>,
                              &by_dtype<&LD::plant_fx, &LF::plant_fx>,
-                             &by_dtype<&LD::plant_load, &LF::plant_load>};
+                             &by_dtype<&LD::plant_load, &LF::plant_load>,
+                             &by_dtype<&LD::contact, &LF::contact>};
     return &o;
   }
 };

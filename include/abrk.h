@@ -337,7 +337,8 @@ int abrk_osc_rollout_twolink_batch(int arm_id, int dtype, const abrk_osc_params*
  *   `substeps` times, h = dt / substeps, u held:  dq += ddq h;  q += dq h     (the update order of
  *   abr_control/arms/twojoint/arm_sim.py:131-132; arms/threejoint/arm_sim.py:93-94 takes dt/1e-5 such substeps)
  * gravity = 0 leaves g out.  These two entry points are the nominal plant; joint friction, joint limits, torque
- * saturation and external loads are the *_fx entry points below.  No contacts.
+ * saturation and external loads are the *_fx entry points below, a payload the *_payload ones, and contact of the end
+ * effector with planes is abrk_contact_step_batch, whose torque arrives as tau_ext.
  * A row whose M has a non-positive Cholesky pivot is reported as ABRK_ESINGULAR exactly as by
  * abrk_osc_generate_batch: host arrays - the call returns the code; device pointers - the stream's next sync does.
  * --------------------------------------------------------------------------------- */
@@ -422,6 +423,57 @@ int abrk_forward_dynamics_payload_batch(int arm_id, int dtype, const abrk_plant_
 int abrk_plant_step_payload_batch(int arm_id, int dtype, const abrk_plant_params* params, const abrk_plant_effects* fx,
                                   int64_t B, void* q, void* dq, const void* u, const void* tau_ext, const void* wrench,
                                   const void* payload, int device, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * End-effector contact with per-row planes, and a force report.  One kernel per tick that WRITES the plant's
+ * joint-space disturbance: record { law; abrk_contact_step_batch -> tau; abrk_plant_step_fx_batch(tau_ext = tau) } and
+ * the arm can press on a table, slide along it and lift off inside a replayed plan.  The plant kernels are untouched.
+ *
+ * Row b has the contact point p = Tx(frame, q, x = off) - `frame` any frame of robot_config.Tx, `off` a tool offset in
+ * that frame, shared by the batch - with a sphere tip of radius rho around it, and S half-spaces of its own,
+ * `surface` [B,S,8] of `dtype` = nx, ny, nz, d, k, c, mu, rho; the free side is n.x > d.  With Jp = J(frame, q, x = off)[:3]
+ * and v = Jp dq each surface contributes
+ *   delta = d + rho - n.p                   penetration; delta <= 0: nothing
+ *   vn    = n.v                             > 0 leaving
+ *   fn    = max(0, k delta - c vn)          Kelvin-Voigt, no adhesion
+ *   vt    = v - vn n
+ *   f     = fn n - mu fn vt / sqrt(|vt|^2 + vs^2)       Coulomb friction smoothed like coulomb_vs of abrk_plant_effects
+ * and with F the sum of f over the row's surfaces
+ *   tau_c = Jp^T F                          written to tau [B,n], or added to it (accumulate != 0)
+ * n is used as given (the kernel does not normalise it).  Columns of Jp of joints past `frame` are zero, as in
+ * robot_config.J, so those entries of tau_c are exact zeros; a row clear of every surface gets tau_c = 0 exactly.
+ * `report` [B,8] (optional) is what a wrist force sensor and a logger want: F in the world frame [3]; R(frame, q)^T F,
+ * the same force in the frame's own coordinates [3]; the deepest delta of the row (negative: clear of every surface);
+ * the number of surfaces with delta > 0.
+ *
+ * LIMITATION: the force is evaluated ONCE per tick from the state at the start of the tick, and the plant holds it over
+ * its substeps like u - the price of leaving the plant kernels alone.  The contact spring is therefore sampled with the
+ * TICK h = dt, whatever `substeps` is.  With m_eff = 1 / (n^T Jp M^-1 Jp^T n) the arm's effective mass along the normal,
+ * A = k h^2 / m_eff and D = c h / m_eff, the linearised contact is stable
+ *   substeps = 1 (the plant's dq += ddq h; q += dq h):   A + 2 D < 4
+ *   many substeps (a force held over an exact step):     A / 2 < D < 2, i.e. k h / 2 < c < 2 m_eff / h
+ * so more substeps do NOT stiffen the contact, and with them an undamped plane (c = 0) gains energy at every bounce.
+ * Keep A below about 1 and c above k h / 2 (k = 1e4 N/m, h = 1 ms: m_eff > 0.01 kg, c > 5 N s/m).
+ * More than one contact point: one call per point, the later ones with accumulate.
+ *
+ * Recordable into a plan like every entry point: `surface` is read with ordinary loads at every launch, so a plane
+ * moved or softened between two replays takes effect.  A HOST surface array is validated before it is staged -
+ * | |n| - 1 | > 1e-6, a negative k, c, mu or rho, anything non-finite: ABRK_EINVAL with the row and the surface in the
+ * message.  A DEVICE array is NOT validated, as with the payload.  ABRK_EINVAL also for params: a frame outside the arm,
+ * a non-finite off, n_surfaces outside 1..ABRK_CONTACT_MAX_SURFACES, vs <= 0.
+ * --------------------------------------------------------------------------------- */
+#define ABRK_CONTACT_MAX_SURFACES 4
+typedef struct abrk_contact_params {
+  int32_t frame;        /* link_i -> 2i, joint_i -> 2i+1, EE -> 2N+1: the loop recorder's encoding */
+  double off[3];
+  int32_t n_surfaces;   /* 1..ABRK_CONTACT_MAX_SURFACES */
+  double vs;            /* > 0 */
+  int32_t accumulate;
+} abrk_contact_params;
+
+int abrk_contact_step_batch(int arm_id, int dtype, const abrk_contact_params* params, int64_t B, const void* q,
+                            const void* dq, const void* surface, void* tau, void* report /* or NULL */, int device,
+                            void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Iterative inverse kinematics: InverseKinematics.generate_path

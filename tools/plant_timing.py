@@ -21,6 +21,14 @@ point with everything on, payload entry point with nothing else, and with everyt
 10 cm of the end effector, every seventh row without a mass.  Same rounds, same table form, ratios to the plain step.
 
     python tools/plant_timing.py --payload [--rows-fx 1048576]
+
+--contact: the contact kernel beside the plain plant step (profiles/contact_step.md): UR5 and Jaco2, fp64 and fp32, at
+4096 and 1 M rows - contact.contact_step with one and with four surfaces per row and the report on, a third of the rows
+pressing, a third clear, a third leaving; and, at 4096 rows, the recorded tick { contact; plant_step(tau_ext) } against
+{ plant_step } per replayed tick.  Same rounds; ratios to the plain step of the same rounds.  bytes_per_row is what the
+kernel reads and writes (q, dq, S surfaces, tau, report), gbytes_per_s that over the median.
+
+    python tools/plant_timing.py --contact [--rows-fx 1048576]
 """
 import argparse
 import json
@@ -110,13 +118,105 @@ def effects_leg(rows_large, payload=False):
     print(json.dumps(res))
 
 
+def contact_leg(rows_large):
+    import abr_control_amd as a
+    from abr_control_amd import _abi, contact, engine
+    from abr_control_amd.arms import jaco2, ur5
+
+    s = a.Stream(0)
+    p = _abi.make_plant_params(1e-3)
+    rounds = 5
+    res = {"leg": "contact", "device": a.device_name(0), "warmup": WARMUP, "timed": TIMED, "rounds": rounds, "us": {}}
+    e0, e1 = a.Event(0), a.Event(0)
+
+    def one_round(fn, per=1):
+        for _ in range(WARMUP):
+            fn()
+        s.sync()
+        ts = []
+        for _ in range(TIMED):
+            e0.record(s)
+            fn()
+            e1.record(s)
+            s.sync()
+            ts.append(e1.elapsed_ms_since(e0) * 1e3 / per)
+        return ts
+
+    for name, make in (("ur5", ur5.Config), ("jaco2", jaco2.Config)):
+        res["us"][name] = {}
+        for dtype in (np.float64, np.float32):
+            rc = make(dtype=dtype)
+            n = rc.N_JOINTS
+            res["us"][name][np.dtype(dtype).name] = {}
+            for B in (4096, rows_large):
+                rng = np.random.RandomState(0)
+                q0, dq0 = rng.uniform(-1.9, 1.9, (B, n)).astype(dtype), rng.uniform(-2, 2, (B, n)).astype(dtype)
+                q, dq = a.DeviceArray.from_numpy(q0), a.DeviceArray.from_numpy(dq0)
+                u = a.DeviceArray.from_numpy(rng.uniform(-20, 20, (B, n)).astype(dtype))
+                # planes through each row's own point: delta = +25 mm (two rows in three) or -25 mm; of the penetrated
+                # ones every other is left faster than its spring pushes (c vn > k delta)
+                xyz = np.asarray(rc.Tx("EE", q0), dtype=np.float64)
+                v = np.einsum("bij,bj->bi", np.asarray(rc.J("EE", q0), dtype=np.float64)[:, :3], dq0.astype(np.float64))
+                tables = {}
+                for S in (1, 4):
+                    nrm = rng.normal(size=(B, S, 3))
+                    nrm /= np.linalg.norm(nrm, axis=2, keepdims=True)
+                    delta = np.where(np.arange(B) % 3 == 1, -0.025, 0.025)[:, None] * np.ones((1, S))
+                    planes = np.zeros((B, S, 8))
+                    planes[:, :, :3] = nrm
+                    planes[:, :, 3] = np.einsum("bsi,bi->bs", nrm, xyz) + delta
+                    planes[:, :, 4:] = [2e4, 100.0, 0.5, 0.0]
+                    planes[2::3, :, 5] = 500.0
+                    tables[S] = a.ContactSurfaces(rc, B, planes.astype(dtype).astype(np.float64), stream=s)
+
+                def reset():
+                    q.copy_from_numpy(q0, stream=s)
+                    dq.copy_from_numpy(dq0, stream=s)
+                    s.sync()
+
+                forms = {
+                    "plain": lambda: engine.plant_step(rc.arm_id, n, p, q, dq, u, dtype=dtype, stream=s),
+                    "contact_s1": lambda: tables[1].apply(q, dq),
+                    "contact_s4": lambda: tables[4].apply(q, dq),
+                }
+                ts = {k: [] for k in forms}
+                for _ in range(rounds):
+                    for k, fn in forms.items():
+                        reset()
+                        ts[k] += one_round(fn)
+                if B == 4096:
+                    with engine.Plan(device=0, stream=s) as bare:
+                        engine.plant_step(rc.arm_id, n, p, q, dq, u, dtype=dtype, stream=s)
+                    with engine.Plan(device=0, stream=s) as tick:
+                        tau = tables[1].apply(q, dq)
+                        engine.plant_step(rc.arm_id, n, p, q, dq, u, dtype=dtype, stream=s, tau_ext=tau)
+                    for k, plan in (("tick_plant_graph", bare), ("tick_contact_plant_graph", tick)):
+                        reset()
+                        ts[k] = one_round(lambda: plan.launch_graph(200), per=200)[:10]
+                out = {k: {"median_us": float(np.median(v)), "min_us": float(np.min(v)), "max_us": float(np.max(v))}
+                       for k, v in ts.items()}
+                esz = np.dtype(dtype).itemsize
+                for k, S in (("contact_s1", 1), ("contact_s4", 4)):
+                    out[k]["ratio_to_plain"] = out[k]["median_us"] / out["plain"]["median_us"]
+                    out[k]["bytes_per_row"] = (3 * n + 8 * S + 8) * esz
+                    out[k]["gbytes_per_s"] = out[k]["bytes_per_row"] * B / out[k]["median_us"] * 1e-3
+                if B == 4096:
+                    out["tick_contact_plant_graph"]["added_us"] = (out["tick_contact_plant_graph"]["median_us"]
+                                                                   - out["tick_plant_graph"]["median_us"])
+                res["us"][name][np.dtype(dtype).name][str(B)] = out
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows-large", type=int, default=8 << 20)
     ap.add_argument("--effects", action="store_true", help="time the plant with effects against the plain step")
     ap.add_argument("--payload", action="store_true", help="time the payload step against the effects and the plain step")
+    ap.add_argument("--contact", action="store_true", help="time the contact kernel against the plain step")
     ap.add_argument("--rows-fx", type=int, default=1 << 20)
     args = ap.parse_args()
+    if args.contact:
+        return contact_leg(args.rows_fx)
     if args.effects or args.payload:
         return effects_leg(args.rows_fx, payload=args.payload)
     import abr_control_amd as a
