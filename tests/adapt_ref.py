@@ -13,8 +13,9 @@ With a(tau) = 1 - exp(-dt / tau), a(0) = 1:
   7  W += (pes_learning_rate dt / n_per) e_f (x) a_f
 
 Besides the outputs it keeps, per row, how close the spiking decision v > 1 ever came to a tie: the number of
-neuron-steps with |v - 1| < band and the smallest |v - 1| seen - rows and cases where another arithmetic may decide
-differently are recognised by them."""
+neuron-steps with |v - 1| < band and the smallest |v - 1| seen, and per neuron whether any of its steps had
+|v - 1| < band (near_n) - rows, neurons and cases where another arithmetic may decide differently are recognised by
+them."""
 import numpy as np
 
 TAU_PRE = 0.005
@@ -46,6 +47,7 @@ class AdaptRef:
         self.band = band
         self.near = np.zeros(B, dtype=np.int64)  # neuron-steps with |v - 1| < band
         self.margin = np.full(B, np.inf)         # smallest |v - 1| at a threshold decision
+        self.near_n = np.zeros((B, N), dtype=bool)  # neurons with any step at which |v - 1| < band
 
     def state(self):
         return {"x_f": self.x_f, "e_f": self.e_f, "v": self.v, "ref": self.ref, "a_f": self.a_f, "W": self.W,
@@ -58,6 +60,7 @@ class AdaptRef:
         self.v -= (J - self.v) * np.expm1(-delta / self.tau_rc)
         gap = np.abs(self.v - 1.0)
         self.near += np.sum(gap < self.band, axis=1)
+        self.near_n |= gap < self.band
         self.margin = np.minimum(self.margin, gap.min(axis=1))
         spiked = self.v > 1.0
         over, den = self.v - 1.0, J - 1.0

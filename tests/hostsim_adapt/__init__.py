@@ -24,11 +24,12 @@ def lib():
 
 
 class HostAdapt:
-    """B rows of the adaptive signal stepped by the host build, with the constructor and tick() of adapt_ref.AdaptRef"""
+    """B rows of the adaptive signal stepped by the host build, with the constructor and tick() of adapt_ref.AdaptRef.
+    split: (w0, w1) - tick() then hands its x_in to the row program in two arrays, in0 [B,w0] and in1 [B,w1]"""
 
     def __init__(self, enc, gain, bias, B, n_output, n_per, neuron_type="lif", shift=None, scale=None, dt=0.001,
                  tau_input=0.012, tau_training=0.012, tau_output=0.2, tau_rc=0.02, tau_ref=0.002,
-                 pes_learning_rate=1e-6, W0=None):
+                 pes_learning_rate=1e-6, W0=None, split=None):
         f8 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
         self.enc, self.gain, self.bias = f8(enc), f8(gain), f8(bias)
         N, D = self.enc.shape
@@ -37,6 +38,7 @@ class HostAdapt:
         self.head = ({"lif": 0, "lif_rate": 1}[neuron_type], D, n_output, N, n_per)
         self.taus = (dt, tau_input, tau_training, tau_output, tau_rc, tau_ref, pes_learning_rate)
         O, self.B = n_output, B
+        self.split = split
         self.st = {"x_f": np.zeros((B, D)), "e_f": np.zeros((B, O)), "v": np.zeros((B, N)), "ref": np.zeros((B, N)),
                    "a_f": np.zeros((B, N)), "W": np.zeros((B, O, N)), "out_f": np.zeros((B, O))}
         if W0 is not None:
@@ -47,6 +49,8 @@ class HostAdapt:
 
     def tick(self, x_in, training, in1=None, u_add=None):
         f8 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        if self.split is not None and in1 is None:
+            x_in, in1 = np.asarray(x_in)[:, :self.split[0]], np.asarray(x_in)[:, self.split[0]:]
         x_in, training = f8(x_in), f8(training)
         in1 = None if in1 is None else f8(in1)
         out = np.zeros((self.B, self.head[2]))
