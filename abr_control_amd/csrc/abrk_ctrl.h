@@ -2660,11 +2660,16 @@ ABRK_INL void ik_row(const A& arm, const IkP<T>& P, T (&q)[A::N], const T (&tgt)
       T sc = P.max_dq * rcp(m);
       sfor<N>([&](auto i) ABRK_LAMBDA { dq[i()] *= sc; });
     }
-    sfor<N>([&](auto i) ABRK_LAMBDA {
-      ppath[ii * N + i()] = q[i()];
-      vpath[ii * N + i()] = dq[i()];
-      q[i()] += dq[i()];
-    });
+    {
+      // the step taken is the step stored (inverse_kinematics.py:132-134): contracted, the clamp's dq * sc went into
+      // q as one fused multiply-add and position_path[t + 1] != position_path[t] + velocity_path[t] in the last bit
+#pragma clang fp contract(off)
+      sfor<N>([&](auto i) ABRK_LAMBDA {
+        ppath[ii * N + i()] = q[i()];
+        vpath[ii * N + i()] = dq[i()];
+        q[i()] = q[i()] + dq[i()];
+      });
+    }
   }
 }
 
