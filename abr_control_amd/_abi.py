@@ -374,6 +374,39 @@ def make_contact_params(n, frame="EE", offset=(0, 0, 0), n_surfaces=1, vs=1e-3, 
     return p
 
 
+FORCE_CMD = ("nx", "ny", "nz", "f_des")  # the columns of cmd [B,4]
+FORCE_GAINS = ("kp", "kv", "kf", "ki", "i_max", "kvf", "f_touch", "v_app", "kv_null")
+
+
+class ForceParams(C.Structure):
+    """abrk_force_params (include/abrk.h)"""
+    _fields_ = [("frame", C.c_int32), ("off", C.c_double * 3)] + [(k, C.c_double) for k in FORCE_GAINS] + [
+        ("dt", C.c_double), ("use_g", C.c_int32), ("accumulate", C.c_int32), ("force_ld", C.c_int32)]
+
+
+def make_force_params(n, frame="EE", offset=(0, 0, 0), kp=100.0, kv=20.0, kf=0.5, ki=20.0, i_max=50.0, kvf=20.0,
+                      f_touch=0.5, v_app=0.05, kv_null=10.0, dt=0.001, use_g=True, accumulate=False, force_ld=3):
+    """Parameters of force_control.force_control_step for an arm of `n` joints: `frame` / `offset` the controlled point
+    as in make_contact_params; kp, kv the motion gains; kf, ki, i_max the force PI loop and its anti-windup clamp; kvf
+    the damping along the normal while in contact; f_touch (N) the sensed normal force above which a row is in
+    contact; v_app (m/s) the approach speed while free; kv_null the null-space damping (0: off); dt (s) the tick;
+    use_g: u -= g(q); accumulate: u += instead of u =; force_ld: values per row of the force array (8: a contact
+    report).  The values are checked by the C entry point."""
+    p = ForceParams()
+    p.frame = int(frame) if isinstance(frame, (int, np.integer)) else frame_id(frame, int(n))
+    off = np.asarray(offset, dtype=float)
+    if off.shape != (3,):
+        raise ValueError(f"offset has shape {off.shape}; expected (3,)")
+    for r in range(3):
+        p.off[r] = off[r]
+    p.kp, p.kv, p.kf, p.ki, p.i_max = float(kp), float(kv), float(kf), float(ki), float(i_max)
+    p.kvf, p.f_touch, p.v_app, p.kv_null, p.dt = float(kvf), float(f_touch), float(v_app), float(kv_null), float(dt)
+    p.use_g = int(bool(use_g))
+    p.accumulate = int(bool(accumulate))
+    p.force_ld = int(force_ld)
+    return p
+
+
 ADAPT_LIF, ADAPT_LIF_RATE = 0, 1  # ABRK_ADAPT_* (include/abrk.h)
 ADAPT_NEURON_TYPES = {"lif": ADAPT_LIF, "lif_rate": ADAPT_LIF_RATE}
 ADAPT_MAX_INPUT, ADAPT_MAX_OUTPUT = 64, 16

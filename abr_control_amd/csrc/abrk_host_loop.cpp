@@ -1,5 +1,5 @@
 // abrk_host_loop.cpp - what a closed loop adds around the law: two-link step and rollout, the rigid-body plant, the
-// loop recorder, end-effector contact, the path planner, the adaptive signal and the measurement channel.
+// loop recorder, end-effector contact, the force-control law, the path planner, the adaptive signal and the measurement channel.
 #include <cmath>
 
 #include "abrk_host.h"
@@ -406,6 +406,100 @@ extern "C" int abrk_contact_step_batch(int arm_id, int dtype, const abrk_contact
   if (int rc = st.reserve()) return rc;
   const auto pb = blocks([&](auto t) { return make_contactp<decltype(t)>(*P, n); });
   return launch_arm(st, a, dtype, B, &ArmOps::contact, ca, pb);
+}
+
+// ------------------------------------------------------------------------------- force-controlled contact
+namespace {
+template <class T>
+ForceP<T> make_forcep(const abrk_force_params& P, int n) {
+  ForceP<T> p;
+  p.frame = P.frame;
+  p.m = frame_m(P.frame, n);
+  for (int r = 0; r < 3; r++) p.off[r] = T(P.off[r]);
+  p.kp = T(P.kp);
+  p.kv = T(P.kv);
+  p.kf = T(P.kf);
+  p.ki = T(P.ki);
+  p.i_max = T(P.i_max);
+  p.kvf = T(P.kvf);
+  p.f_touch = T(P.f_touch);
+  p.v_app = T(P.v_app);
+  p.kv_null = T(P.kv_null);
+  p.dt = T(P.dt);
+  p.use_g = P.use_g ? 1 : 0;
+  p.accumulate = P.accumulate ? 1 : 0;
+  p.force_ld = P.force_ld;
+  p.status = nullptr;
+  return p;
+}
+// A host command array [B, 4] = nx, ny, nz, f_des of `dtype`, looked at where it is about to be staged: everything
+// finite, | |n| - 1 | <= 1e-6, f_des >= 0.  (A device array is taken as it is.)
+int check_cmd_host(int dtype, int64_t B, const void* cmd) {
+  static const char* const names[4] = {"nx", "ny", "nz", "f_des"};
+  for (int64_t b = 0; b < B; b++) {
+    double v[4];
+    for (int k = 0; k < 4; k++) {
+      const int64_t at = b * 4 + k;
+      if (dtype == ABRK_F64) {
+        memcpy(&v[k], static_cast<const char*>(cmd) + at * 8, 8);
+      } else {
+        float f;
+        memcpy(&f, static_cast<const char*>(cmd) + at * 4, 4);
+        v[k] = f;
+      }
+      if (!finite_at(&v[k])) return fail(ABRK_EINVAL, "cmd: row %lld: %s is not finite", (long long)b, names[k]);
+    }
+    if (v[3] < 0) return fail(ABRK_EINVAL, "cmd: row %lld: f_des=%g is negative", (long long)b, v[3]);
+    const double len = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    if (!(std::fabs(len - 1.0) <= 1e-6))
+      return fail(ABRK_EINVAL, "cmd: row %lld: |n|=%.9g is not 1 to within 1e-6", (long long)b, len);
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" int abrk_force_control_batch(int arm_id, int dtype, const abrk_force_params* P, int64_t B, const void* q,
+                                        const void* dq, const void* target, const void* target_velocity,
+                                        const void* cmd, const void* force, void* integ, void* u, int device,
+                                        void* stream) {
+  ArmEntry* a;
+  if (int rc = check_common(arm_id, dtype, B, &a)) return rc;
+  if (!a->ops->force) return fail(ABRK_EINVAL, "this arm's kernels carry no force-control law (rebuild its plugin)");
+  if (!P) return fail(ABRK_EINVAL, "params is NULL");
+  const int n = a->desc.n_joints;
+  if (P->frame < 0 || P->frame > 2 * n + 1) return fail(ABRK_EINVAL, "Invalid transformation name: frame id %d", P->frame);
+  for (int r = 0; r < 3; r++)
+    if (!finite_at(&P->off[r])) return fail(ABRK_EINVAL, "off[%d] is not finite", r);
+  const struct {
+    const char* name;
+    const double* v;
+  } nonneg[] = {{"kp", &P->kp},     {"kv", &P->kv},           {"kf", &P->kf},       {"ki", &P->ki},          {"i_max", &P->i_max},
+                {"kvf", &P->kvf},   {"f_touch", &P->f_touch}, {"v_app", &P->v_app}, {"kv_null", &P->kv_null}};
+  for (const auto& g : nonneg)
+    if (!nonnegative_finite_at(g.v)) return fail(ABRK_EINVAL, "%s=%g is not a finite value >= 0", g.name, *g.v);
+  if (!positive_finite_at(&P->dt)) return fail(ABRK_EINVAL, "dt=%g is not a finite value > 0", P->dt);
+  if (P->force_ld < 3) return fail(ABRK_EINVAL, "force_ld=%d < 3", P->force_ld);
+  if (!q || !dq || !target || !cmd || !force || !integ || !u)
+    return fail(ABRK_EINVAL, "q, dq, target, cmd, force, integ and u are required");
+  if (B == 0) return 0;
+  if (!device_view(cmd))
+    if (int rc = check_cmd_host(dtype, B, cmd)) return rc;
+  if (int rc = use_device(device)) return rc;
+  const size_t s = esz(dtype);
+  Stager st{device, (hipStream_t)stream};
+  ForceArgs fa{};
+  st.in(&fa.q, q, (size_t)B * n * s);
+  st.in(&fa.dq, dq, (size_t)B * n * s);
+  st.in(&fa.target, target, (size_t)B * 6 * s);
+  st.in(&fa.tv, target_velocity, (size_t)B * 6 * s);
+  st.in(&fa.cmd, cmd, (size_t)B * 4 * s);
+  st.in(&fa.force, force, (size_t)B * P->force_ld * s);
+  st.inout(&fa.integ, integ, (size_t)B * s);
+  // (accumulate: u goes in as well as out)
+  st.bind(&fa.u, u, (size_t)B * n * s, P->accumulate != 0, true);
+  if (int rc = st.reserve()) return rc;
+  auto pb = blocks([&](auto t) { return make_forcep<decltype(t)>(*P, n); });
+  return with_status_word(st, pb, nullptr, [&] { return launch_arm(st, a, dtype, B, &ArmOps::force, fa, pb); });
 }
 
 // ------------------------------------------------------------------------------- path planner

@@ -9,6 +9,7 @@
 #include "abrk_select.h"
 #include "abrk_trace.h"
 #include "abrk_contact.h"
+#include "abrk_force.h"
 
 namespace abrk {
 
@@ -609,6 +610,22 @@ contact_kernel(A arm, ContactP<T> P, long B, ContactIO<T> io) {
   contact_body<A, T>(b, arm, P, io);
 }
 
+// Force-controlled contact (abrk_force.h force_body): the dynamics pass of the task-space Floating kernel plus the
+// frame capture of the contact kernel, one lane per row.  Two waves per SIMD: the 256-register line holds the six-joint
+// fp64 row of a compile-time table without scratch (UR5 188, Jaco2 236); the fp64 row of a runtime table does not fit it
+// (six joints: 255 registers and 228 B of scratch) and takes the registers it needs at one wave per SIMD, like the
+// Floating kernel (profiles/force_control.md).  The mode switch is a per-lane select, not a branch.
+template <class A, class T>
+constexpr int force_min_waves() {
+  return (A::kStatic || sizeof(T) < 8) ? 2 : kMinWaves;
+}
+template <class A, class T>
+__global__ void __launch_bounds__(kBlock, (force_min_waves<A, T>()))
+force_kernel(A arm, ForceP<T> P, long B, ForceIO<T> io) {
+  ABRK_ROW_INDEX
+  force_body<A, T>(b, arm, P, io);
+}
+
 template <class A, class T>
 __global__ void __launch_bounds__(kBlock, kMinWaves)
 ik_kernel(A arm, IkP<T> P, long B, const T* __restrict__ qg, const T* __restrict__ tg, T* __restrict__ pp,
@@ -804,6 +821,11 @@ struct ContactArgs {
   const void *q, *dq, *surface;
   void *tau, *report;  // report may be null
 };
+struct ForceArgs {
+  const void* P;  // ForceP<T>
+  const void *q, *dq, *target, *tv, *cmd, *force;  // tv may be null
+  void *integ, *u;
+};
 struct LawArgs {
   const void* P;  // OscP<T>
   const void *J, *M, *g, *c, *xyz, *R, *q, *dq, *target, *tv, *une;
@@ -858,6 +880,7 @@ struct ArmOps {
   hipError_t (*plant_fx)(int dtype, const LaunchArgs&, const PlantFxArgs&);
   hipError_t (*plant_load)(int dtype, const LaunchArgs&, const PlantLoadArgs&);
   hipError_t (*contact)(int dtype, const LaunchArgs&, const ContactArgs&);
+  hipError_t (*force)(int dtype, const LaunchArgs&, const ForceArgs&);
 };
 hipError_t launch_twolink_step(int dtype, const LaunchArgs& la, const void* K, void* q, void* dq, const void* u);
 
@@ -994,6 +1017,13 @@ struct Launch {
                        *static_cast<const ContactP<T>*>(a.P), la.B, io);
     return hipGetLastError();
   }
+  static hipError_t force(const LaunchArgs& la, const ForceArgs& a) {
+    const ForceIO<T> io{(const T*)a.q,   (const T*)a.dq,    (const T*)a.target, (const T*)a.tv,
+                        (const T*)a.cmd, (const T*)a.force, (T*)a.integ,        (T*)a.u};
+    hipLaunchKernelGGL((force_kernel<A, T>), grid_for(la.B), dim3(kBlock), 0, la.stream, arm_of(la),
+                       *static_cast<const ForceP<T>*>(a.P), la.B, io);
+    return hipGetLastError();
+  }
   static hipError_t rollout(const LaunchArgs& la, const RolloutArgs& a) {
     if constexpr (A::N == 2) {
       with_rollout_variant(a.fast, a.use_C != 0, [&](auto uc, auto km) {
@@ -1058,7 +1088,8 @@ struct OpsFor {
                              &by_dtype<&LD::trace, &LF::trace>,
                              &by_dtype<&LD::plant_fx, &LF::plant_fx>,
                              &by_dtype<&LD::plant_load, &LF::plant_load>,
-                             &by_dtype<&LD::contact, &LF::contact>};
+                             &by_dtype<&LD::contact, &LF::contact>,
+                             &by_dtype<&LD::force, &LF::force>};
     return &o;
   }
 };

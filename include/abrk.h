@@ -476,6 +476,60 @@ int abrk_contact_step_batch(int arm_id, int dtype, const abrk_contact_params* pa
                             void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Force-controlled contact: Khatib's unified motion/force law for the point of abrk_contact_step_batch.  One kernel per
+ * tick that writes u: record { abrk_force_control_batch(force = the contact report of the previous tick) -> u;
+ * abrk_contact_step_batch -> tau, report; abrk_plant_step_fx_batch(u, tau_ext = tau) } and an arm approaches a surface,
+ * presses on it with a commanded force and moves along it inside a replayed plan.
+ *
+ * Row b has the point p = Tx(frame, q, x = off), Jp = J(frame, q, x = off)[:3], v = Jp dq, and M, g as robot_config
+ * returns them.  Its inputs: `target` [B,6] as abrk_osc_generate_batch takes it, of which only x_d = columns 0..2 are
+ * read; `target_velocity` [B,6] or NULL, v_d = columns 0..2 (NULL: 0); `cmd` [B,4] = nx, ny, nz, f_des - n the surface
+ * normal, a unit vector in the world frame that points INTO FREE SPACE, f_des >= 0 the force the tip shall press with
+ * (N); `force` [B, force_ld], columns 0..2 the sensed force F ON the tip in the world frame (force_ld = 8: a contact
+ * `report` array as it is); `integ` [B], the force integral, read and written.
+ *   A    = Jp M^-1 Jp^T
+ *   Mx   = inv(A) where det(A) > 1e-3, else pinv(A, rcond = 1e-4)          the rule of the task-space Floating law
+ *   a    = kp (x_d - p) + kv (v_d - v);   a_n = n.a;   v_n = n.v;   f_m = n.F
+ *   in contact (f_m > f_touch):
+ *          e   = f_des - f_m                                                > 0: pressing too lightly
+ *          I'  = clamp(I + ki e dt, -i_max, +i_max)
+ *          F_c = Mx (a - a_n n - kvf v_n n) - (f_des + kf e + I') n         pushes along -n, into the surface
+ *   free (otherwise):
+ *          I'  = 0
+ *          F_c = Mx (a - a_n n + kv (-v_app - v_n) n)                       approaches along -n at v_app
+ *   u    = Jp^T F_c - [use_g] g(q) - kv_null (M dq - Jp^T Mx v)
+ *   integ <- I';  u written to u [B,n], or added to it (accumulate != 0)
+ * The last term of u is the Damping law, -kv_null M dq, passed through OSC's null-space filter I - Jp^T Mx Jp M^-1.
+ * use_g has OSC's sign (u -= g).  n is used as given (the kernel does not normalise it).  The two modes are a per-lane
+ * select: a row's mode may differ from its neighbour's and change from tick to tick.
+ * NOT MODELLED: orientation (no rotational rows: the wrist is left to the null-space damping); more than one
+ * constrained direction; Coriolis compensation; a moment about the point.
+ *
+ * Recordable into a plan like every entry point, host or device pointers, re-entrant per stream.  `cmd` is read with
+ * ordinary loads at every launch, so a normal or a desired force rewritten between two replays takes effect.  A HOST cmd
+ * array is validated before it is staged - | |n| - 1 | > 1e-6, f_des < 0, anything non-finite: ABRK_EINVAL with the row
+ * in the message.  A DEVICE array is NOT validated, as with the payload and the contact surfaces.  ABRK_EINVAL also for
+ * params: a frame outside the arm, a non-finite off, a negative or non-finite gain, f_touch, v_app, i_max or kv_null,
+ * dt <= 0, force_ld < 3.  ABRK_ESINGULAR for a non-positive Cholesky pivot of M, as in the other laws.
+ * --------------------------------------------------------------------------------- */
+typedef struct abrk_force_params {
+  int32_t frame;        /* as abrk_contact_params */
+  double off[3];
+  double kp, kv;        /* motion gains (>= 0) */
+  double kf, ki, i_max; /* force PI, anti-windup clamp (>= 0) */
+  double kvf;           /* damping along n while in contact (>= 0) */
+  double f_touch;       /* >= 0: in contact where n.F exceeds it */
+  double v_app;         /* >= 0: approach speed along -n while free */
+  double kv_null;       /* >= 0; 0 switches the null-space damping off */
+  double dt;            /* > 0 */
+  int32_t use_g, accumulate, force_ld; /* force_ld >= 3 */
+} abrk_force_params;
+
+int abrk_force_control_batch(int arm_id, int dtype, const abrk_force_params* params, int64_t B, const void* q,
+                             const void* dq, const void* target, const void* target_velocity /* or NULL */,
+                             const void* cmd, const void* force, void* integ, void* u, int device, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Iterative inverse kinematics: InverseKinematics.generate_path
  * (abr_control/controllers/path_planners/inverse_kinematics.py:28-135) for B independent paths, all
  * n_timesteps iterations of a path inside one kernel (each iteration: Tx, J, quaternion of the EE, two

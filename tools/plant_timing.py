@@ -29,6 +29,14 @@ pressing, a third clear, a third leaving; and, at 4096 rows, the recorded tick {
 kernel reads and writes (q, dq, S surfaces, tau, report), gbytes_per_s that over the median.
 
     python tools/plant_timing.py --contact [--rows-fx 1048576]
+
+--force: the force-control law beside the contact step and the plain plant step of the same run
+(profiles/force_control.md): UR5 and Jaco2, fp64 and fp32, at 4096 and 1 M rows - ForceController.generate reading a
+[B,8] report, two rows in three in contact (every third free), every option on; contact.contact_step with one surface
+and the report on; and, at 4096 rows, the recorded tick { force law; contact; plant_step(tau_ext) } against
+{ plant_step } per replayed tick.  The protocol of --contact: same rounds, ratios to the plain step of the same rounds.
+
+    python tools/plant_timing.py --force [--rows-fx 1048576]
 """
 import argparse
 import json
@@ -207,14 +215,113 @@ def contact_leg(rows_large):
     print(json.dumps(res))
 
 
+def force_leg(rows_large):
+    import abr_control_amd as a
+    from abr_control_amd import _abi, engine
+    from abr_control_amd.arms import jaco2, ur5
+
+    s = a.Stream(0)
+    p = _abi.make_plant_params(1e-3)
+    rounds = 5
+    res = {"leg": "force", "device": a.device_name(0), "warmup": WARMUP, "timed": TIMED, "rounds": rounds, "us": {}}
+    e0, e1 = a.Event(0), a.Event(0)
+
+    def one_round(fn, per=1):
+        for _ in range(WARMUP):
+            fn()
+        s.sync()
+        ts = []
+        for _ in range(TIMED):
+            e0.record(s)
+            fn()
+            e1.record(s)
+            s.sync()
+            ts.append(e1.elapsed_ms_since(e0) * 1e3 / per)
+        return ts
+
+    for name, make in (("ur5", ur5.Config), ("jaco2", jaco2.Config)):
+        res["us"][name] = {}
+        for dtype in (np.float64, np.float32):
+            rc = make(dtype=dtype)
+            n = rc.N_JOINTS
+            res["us"][name][np.dtype(dtype).name] = {}
+            for B in (4096, rows_large):
+                rng = np.random.RandomState(0)
+                q0, dq0 = rng.uniform(-1.9, 1.9, (B, n)).astype(dtype), rng.uniform(-2, 2, (B, n)).astype(dtype)
+                q, dq = a.DeviceArray.from_numpy(q0), a.DeviceArray.from_numpy(dq0)
+                u = a.DeviceArray.from_numpy(rng.uniform(-20, 20, (B, n)).astype(dtype))
+                xyz = np.asarray(rc.Tx("EE", q0), dtype=np.float64)
+                nrm = rng.normal(size=(B, 3))
+                nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+                # the contact step of the --contact leg with one surface: delta = +-25 mm through each row's own point
+                planes = np.zeros((B, 1, 8))
+                planes[:, 0, :3] = nrm
+                planes[:, 0, 3] = np.einsum("bi,bi->b", nrm, xyz) + np.where(np.arange(B) % 3 == 1, -0.025, 0.025)
+                planes[:, 0, 4:] = [2e4, 100.0, 0.5, 0.0]
+                table = a.ContactSurfaces(rc, B, planes.astype(dtype).astype(np.float64), stream=s)
+                # the law: a sensed force of 2 - 30 N along n on two rows in three, none on the others
+                sensed = np.zeros((B, 8))
+                sensed[:, :3] = nrm.astype(dtype) * np.where(np.arange(B) % 3 == 1, 0.0, rng.uniform(2, 30, B))[:, None]
+                report = a.DeviceArray.from_numpy(sensed.astype(dtype))
+                tgt = np.zeros((B, 6))
+                tgt[:, :3] = xyz + rng.uniform(-0.1, 0.1, (B, 3))
+                tgt, tv = (a.DeviceArray.from_numpy(x.astype(dtype)) for x in (tgt, rng.uniform(-0.5, 0.5, (B, 6))))
+                press = a.ForceController(rc, B, nrm.astype(dtype).astype(np.float64), rng.uniform(1, 40, B), dt=1e-3,
+                                          stream=s)
+
+                def reset():
+                    q.copy_from_numpy(q0, stream=s)
+                    dq.copy_from_numpy(dq0, stream=s)
+                    press.reset()
+                    s.sync()
+
+                forms = {
+                    "plain": lambda: engine.plant_step(rc.arm_id, n, p, q, dq, u, dtype=dtype, stream=s),
+                    "contact_s1": lambda: table.apply(q, dq),
+                    "force": lambda: press.generate(q, dq, tgt, report, target_velocity=tv),
+                }
+                ts = {k: [] for k in forms}
+                for _ in range(rounds):
+                    for k, fn in forms.items():
+                        reset()
+                        ts[k] += one_round(fn)
+                if B == 4096:
+                    with engine.Plan(device=0, stream=s) as bare:
+                        engine.plant_step(rc.arm_id, n, p, q, dq, u, dtype=dtype, stream=s)
+                    with engine.Plan(device=0, stream=s) as tick:
+                        uf = press.generate(q, dq, tgt, table.device_arrays()["report"], target_velocity=tv)
+                        tau = table.apply(q, dq)
+                        engine.plant_step(rc.arm_id, n, p, q, dq, uf, dtype=dtype, stream=s, tau_ext=tau)
+                    for k, plan in (("tick_plant_graph", bare), ("tick_force_contact_plant_graph", tick)):
+                        reset()
+                        ts[k] = one_round(lambda: plan.launch_graph(200), per=200)[:10]
+                out = {k: {"median_us": float(np.median(v)), "min_us": float(np.min(v)), "max_us": float(np.max(v))}
+                       for k, v in ts.items()}
+                esz = np.dtype(dtype).itemsize
+                for k in ("contact_s1", "force"):
+                    out[k]["ratio_to_plain"] = out[k]["median_us"] / out["plain"]["median_us"]
+                out["force"]["ratio_to_contact"] = out["force"]["median_us"] / out["contact_s1"]["median_us"]
+                # q, dq, u; 3 of target, target_velocity and force each (their lines are fetched whole); cmd; integ twice
+                out["force"]["bytes_per_row"] = (3 * n + 9 + 4 + 2) * esz
+                out["force"]["gbytes_per_s"] = out["force"]["bytes_per_row"] * B / out["force"]["median_us"] * 1e-3
+                if B == 4096:
+                    out["tick_force_contact_plant_graph"]["added_us"] = (
+                        out["tick_force_contact_plant_graph"]["median_us"] - out["tick_plant_graph"]["median_us"])
+                res["us"][name][np.dtype(dtype).name][str(B)] = out
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows-large", type=int, default=8 << 20)
     ap.add_argument("--effects", action="store_true", help="time the plant with effects against the plain step")
     ap.add_argument("--payload", action="store_true", help="time the payload step against the effects and the plain step")
     ap.add_argument("--contact", action="store_true", help="time the contact kernel against the plain step")
+    ap.add_argument("--force", action="store_true", help="time the force-control law against the contact and plain steps")
     ap.add_argument("--rows-fx", type=int, default=1 << 20)
     args = ap.parse_args()
+    if args.force:
+        return force_leg(args.rows_fx)
     if args.contact:
         return contact_leg(args.rows_fx)
     if args.effects or args.payload:
