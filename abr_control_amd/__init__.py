@@ -9,6 +9,7 @@ from . import arms, controllers  # noqa: F401
 from ._lib import AbrkError, DeviceArray, Event, Stream, device_count, device_name, scratch_stats  # noqa: F401
 from .contact import ContactSurfaces  # noqa: F401
 from .force_control import ForceController  # noqa: F401
+from .link_contact import Obstacles  # noqa: F401
 from .recorder import LoopRecorder  # noqa: F401
 from .sensing import JointSensor, SignalChannel  # noqa: F401
 

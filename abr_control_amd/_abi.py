@@ -407,6 +407,36 @@ def make_force_params(n, frame="EE", offset=(0, 0, 0), kp=100.0, kv=20.0, kf=0.5
     return p
 
 
+LINK_CONTACT_MAX_OBSTACLES = 8  # ABRK_LINK_CONTACT_MAX_OBSTACLES (include/abrk.h)
+LINK_CONTACT_MAX_SEGMENTS = 7
+LINK_OBSTACLE = ("cx", "cy", "cz", "R", "k", "c", "mu")  # the columns of obstacle [B,K,7]
+
+
+class LinkContactParams(C.Structure):
+    """abrk_link_contact_params (include/abrk.h)"""
+    _fields_ = [("n_obstacles", C.c_int32), ("link_radius", C.c_double * 7), ("vs", C.c_double),
+                ("accumulate", C.c_int32)]
+
+
+def make_link_contact_params(n, n_obstacles=1, link_radius=0.04, vs=1e-3, accumulate=False):
+    """Parameters of link_contact.link_contact_step for an arm of `n` joints: `n_obstacles` the spheres per row (1..8),
+    `link_radius` the radius of the segment capsules, a scalar or `n` values (< 0: that segment is off), `vs` the
+    smoothing speed of the friction law (m/s), `accumulate`: tau += instead of tau =.  The values are checked by the C
+    entry point."""
+    p = LinkContactParams()
+    p.n_obstacles = int(n_obstacles)
+    r = np.asarray(link_radius, dtype=float)
+    if r.ndim == 0:
+        r = np.full(int(n), float(r))
+    if r.shape != (int(n),):
+        raise ValueError(f"link_radius has shape {r.shape}; expected a scalar or ({int(n)},)")
+    for i in range(LINK_CONTACT_MAX_SEGMENTS):
+        p.link_radius[i] = r[i] if i < int(n) else -1.0
+    p.vs = float(vs)
+    p.accumulate = int(bool(accumulate))
+    return p
+
+
 ADAPT_LIF, ADAPT_LIF_RATE = 0, 1  # ABRK_ADAPT_* (include/abrk.h)
 ADAPT_NEURON_TYPES = {"lif": ADAPT_LIF, "lif_rate": ADAPT_LIF_RATE}
 ADAPT_MAX_INPUT, ADAPT_MAX_OUTPUT = 64, 16

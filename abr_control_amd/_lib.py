@@ -118,6 +118,8 @@ def lib():
             C.c_int, _vp]
         L.abrk_force_control_batch.argtypes = [C.c_int, C.c_int, C.POINTER(_abi.ForceParams), _i64] + [_vp] * 8 + [
             C.c_int, _vp]
+        L.abrk_link_contact_step_batch.argtypes = [C.c_int, C.c_int, C.POINTER(_abi.LinkContactParams), _i64] + [
+            _vp] * 5 + [C.c_int, _vp]
         L.abrk_adapt_step_batch.argtypes = [C.c_int, C.POINTER(_abi.AdaptParams), _i64] + [_vp] * 6 + [
             C.c_int32, _vp, C.c_int32, _vp, C.POINTER(_abi.AdaptState), _vp, _vp, C.c_int, _vp]
         L.abrk_channel_step_batch.argtypes = [C.c_int, C.POINTER(_abi.ChannelParams), _i64, _vp, C.c_int32, _vp,

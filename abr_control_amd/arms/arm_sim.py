@@ -8,15 +8,17 @@ smoothed Coulomb joint friction, hard joint limits with restitution; send_forces
 carried at the end effector - (m, r) for every arm, or [B, 4] rows of m, rx, ry, rz - which changes M, C and g of the
 plant and which the robot_config (the controller's model) knows nothing of.  `surfaces` are planes the arm can touch: a
 contact.ContactSurfaces, or planes [S, 8] / [B, S, 8] of nx, ny, nz, d, k, c, mu, rho for a tip at the origin of the
-end-effector frame; the contact torque of the state at the start of a step is added to that step's tau_ext."""
+end-effector frame; the contact torque of the state at the start of a step is added to that step's tau_ext.
+`obstacles` are spheres the whole arm can hit: a link_contact.Obstacles, or spheres [K, 7] / [B, K, 7] of cx, cy, cz, R,
+k, c, mu for link capsules of the default radius; their torque is added to tau_ext too, after that of `surfaces`."""
 import numpy as np
 
-from .. import _abi, contact, engine, plant_payload
+from .. import _abi, contact, engine, link_contact, plant_payload
 
 
 class ArmSim:
     def __init__(self, robot_config, dt=0.001, q_init=None, substeps=1, gravity=True, effects=None, payload=None,
-                 surfaces=None):
+                 surfaces=None, obstacles=None):
         self.robot_config = robot_config
         n = robot_config.N_JOINTS
         q0 = q_init if q_init is not None else getattr(robot_config, "START_ANGLES", None)
@@ -30,6 +32,8 @@ class ArmSim:
         self.payload = self._payload_rows(payload)
         self.surfaces = surfaces
         self._contact_report = None
+        self.obstacles = obstacles
+        self._link_contact_report = None
         self.t = 0.0
         self.reset()
 
@@ -71,6 +75,25 @@ class ArmSim:
         row per arm; None before the first step or without surfaces"""
         return None if self._contact_report is None else contact.report_dict(self._contact_report)
 
+    def _link_contact(self, q, dq, dtype):
+        """-> the torque [B, n] of the state (q, dq) on self.obstacles; keeps the report"""
+        rc, B = self.robot_config, q.shape[0]
+        ob = self.obstacles
+        if isinstance(ob, link_contact.Obstacles):
+            spheres, params = link_contact.obstacle_rows(ob.obstacles, B), ob.params()
+        else:
+            spheres = link_contact.obstacle_rows(ob, B)
+            params = _abi.make_link_contact_params(rc.N_JOINTS, n_obstacles=spheres.shape[1])
+        tau, self._link_contact_report = link_contact.link_contact_step(
+            rc.arm_id, rc.N_JOINTS, params, q, dq, spheres.astype(dtype), None, report=True, dtype=dtype,
+            device=rc.device)
+        return tau
+
+    def link_contact_report(self):
+        """the report of the last send_forces: {"force", "depth", "n_contacts", "segment", "obstacle", "t"}
+        (link_contact.report_dict), one row per arm; None before the first step or without obstacles"""
+        return None if self._link_contact_report is None else link_contact.report_dict(self._link_contact_report)
+
     def connect(self):
         self.reset()
 
@@ -87,7 +110,7 @@ class ArmSim:
     def send_forces(self, u, dt=None, tau_ext=None, wrench=None):
         """advance one time step under torques u (arm_sim.py:67-82); tau_ext (n,) or (B, n) and wrench (6,) or (B, 6) are
         loads the controller does not know of; the payload carried is self.payload (set_payload changes it between steps);
-        with surfaces the contact is evaluated first and its torque added to tau_ext"""
+        with surfaces and / or obstacles the contact is evaluated first and its torque added to tau_ext"""
         rc = self.robot_config
         dtype = np.dtype(getattr(rc, "dtype", np.float64))
         single = self.q.ndim == 1
@@ -105,6 +128,9 @@ class ArmSim:
         if self.surfaces is not None:
             tau_c = self._contact(q, dq, dtype)
             ext = tau_c if ext is None else ext + tau_c
+        if self.obstacles is not None:
+            tau_l = self._link_contact(q, dq, dtype)
+            ext = tau_l if ext is None else ext + tau_l
         plant_payload.plant_step(rc.arm_id, rc.N_JOINTS, params, q, dq, u2, dtype=dtype, device=rc.device,
                                  effects=self.effects, tau_ext=ext, wrench=rows(wrench, 6),
                                  payload=rows(self.payload, 4))

@@ -1,5 +1,6 @@
 // abrk_host_loop.cpp - what a closed loop adds around the law: two-link step and rollout, the rigid-body plant, the
-// loop recorder, end-effector contact, the force-control law, the path planner, the adaptive signal and the measurement channel.
+// loop recorder, end-effector contact, whole-arm contact, the force-control law, the path planner, the adaptive signal
+// and the measurement channel.
 #include <cmath>
 
 #include "abrk_host.h"
@@ -500,6 +501,85 @@ extern "C" int abrk_force_control_batch(int arm_id, int dtype, const abrk_force_
   if (int rc = st.reserve()) return rc;
   auto pb = blocks([&](auto t) { return make_forcep<decltype(t)>(*P, n); });
   return with_status_word(st, pb, nullptr, [&] { return launch_arm(st, a, dtype, B, &ArmOps::force, fa, pb); });
+}
+
+// ------------------------------------------------------------------------------- whole-arm contact
+namespace {
+static_assert(ABRK_LINK_CONTACT_MAX_OBSTACLES == kLinkContactMaxObstacles, "abrk.h and abrk_link_contact.h agree on the obstacles of a row");
+static_assert(sizeof(((abrk_link_contact_params*)0)->link_radius) / sizeof(double) == kLinkContactMaxSegments,
+              "abrk.h and abrk_link_contact.h agree on the segments of an arm");
+template <class T>
+LinkContactP<T> make_linkcontactp(const abrk_link_contact_params& P, int n) {
+  LinkContactP<T> p;
+  p.K = P.n_obstacles;
+  for (int i = 0; i < kLinkContactMaxSegments; i++) p.radius[i] = i < n ? T(P.link_radius[i]) : T(-1);
+  p.vs2 = T(P.vs * P.vs);
+  p.accumulate = P.accumulate ? 1 : 0;
+  return p;
+}
+// A host obstacle array [B, K, 7] = cx, cy, cz, R, k, c, mu of `dtype`, looked at where it is about to be staged:
+// everything finite, R > 0, and k, c, mu >= 0.  (A device array is taken as it is.)
+int check_obstacle_host(int dtype, int64_t B, int K, const void* obstacle) {
+  static const char* const names[7] = {"cx", "cy", "cz", "R", "k", "c", "mu"};
+  for (int64_t b = 0; b < B; b++)
+    for (int o = 0; o < K; o++) {
+      double v[7];
+      for (int k = 0; k < 7; k++) {
+        const int64_t at = (b * K + o) * 7 + k;
+        if (dtype == ABRK_F64) {
+          memcpy(&v[k], static_cast<const char*>(obstacle) + at * 8, 8);
+        } else {
+          float f;
+          memcpy(&f, static_cast<const char*>(obstacle) + at * 4, 4);
+          v[k] = f;  // (exact; an infinity or a NaN stays one)
+        }
+        if (!finite_at(&v[k]))
+          return fail(ABRK_EINVAL, "obstacle: row %lld, obstacle %d: %s is not finite", (long long)b, o, names[k]);
+        if (k == 3 && !positive_finite_at(&v[k]))
+          return fail(ABRK_EINVAL, "obstacle: row %lld, obstacle %d: R=%g is not > 0", (long long)b, o, v[k]);
+        if (k >= 4 && !nonnegative_finite_at(&v[k]))
+          return fail(ABRK_EINVAL, "obstacle: row %lld, obstacle %d: %s=%g is negative", (long long)b, o, names[k], v[k]);
+      }
+    }
+  return 0;
+}
+}  // namespace
+
+extern "C" int abrk_link_contact_step_batch(int arm_id, int dtype, const abrk_link_contact_params* P, int64_t B,
+                                            const void* q, const void* dq, const void* obstacle, void* tau, void* report,
+                                            int device, void* stream) {
+  ArmEntry* a;
+  if (int rc = check_common(arm_id, dtype, B, &a)) return rc;
+  if (!a->ops->link_contact) return fail(ABRK_EINVAL, "this arm's kernels carry no link contact step (rebuild its plugin)");
+  if (!P) return fail(ABRK_EINVAL, "params is NULL");
+  const int n = a->desc.n_joints;
+  if (P->n_obstacles < 1 || P->n_obstacles > ABRK_LINK_CONTACT_MAX_OBSTACLES)
+    return fail(ABRK_EINVAL, "n_obstacles=%d outside 1..%d", P->n_obstacles, ABRK_LINK_CONTACT_MAX_OBSTACLES);
+  if (!positive_finite_at(&P->vs)) return fail(ABRK_EINVAL, "vs=%g is not a finite value > 0", P->vs);
+  bool any_on = false;
+  for (int i = 0; i < n; i++) {
+    if (!finite_at(&P->link_radius[i])) return fail(ABRK_EINVAL, "link_radius[%d] is not finite", i);
+    any_on = any_on || P->link_radius[i] >= 0;
+  }
+  if (!any_on) return fail(ABRK_EINVAL, "every segment is switched off (link_radius < 0 for all %d)", n);
+  if (!q || !dq || !obstacle || !tau) return fail(ABRK_EINVAL, "q, dq, obstacle and tau are required");
+  if (B == 0) return 0;
+  const int K = P->n_obstacles;
+  if (!device_view(obstacle))
+    if (int rc = check_obstacle_host(dtype, B, K, obstacle)) return rc;
+  if (int rc = use_device(device)) return rc;
+  const size_t s = esz(dtype);
+  Stager st{device, (hipStream_t)stream};
+  LinkContactArgs ca{};
+  st.in(&ca.q, q, (size_t)B * n * s);
+  st.in(&ca.dq, dq, (size_t)B * n * s);
+  st.in(&ca.obstacle, obstacle, (size_t)B * K * 7 * s);
+  // (accumulate: tau goes in as well as out)
+  st.bind(&ca.tau, tau, (size_t)B * n * s, P->accumulate != 0, true);
+  st.out(&ca.report, report, (size_t)B * 8 * s);
+  if (int rc = st.reserve()) return rc;
+  const auto pb = blocks([&](auto t) { return make_linkcontactp<decltype(t)>(*P, n); });
+  return launch_arm(st, a, dtype, B, &ArmOps::link_contact, ca, pb);
 }
 
 // ------------------------------------------------------------------------------- path planner

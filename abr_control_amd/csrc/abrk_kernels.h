@@ -10,6 +10,7 @@
 #include "abrk_trace.h"
 #include "abrk_contact.h"
 #include "abrk_force.h"
+#include "abrk_link_contact.h"
 
 namespace abrk {
 
@@ -626,6 +627,22 @@ force_kernel(A arm, ForceP<T> P, long B, ForceIO<T> io) {
   force_body<A, T>(b, arm, P, io);
 }
 
+// Whole-arm contact (abrk_link_contact.h link_contact_body): forward kinematics, then per (obstacle, segment) pair the
+// closest point and - behind a branch - the Jacobian columns of that point, one lane per row.  Two waves per SIMD on a
+// compile-time table and in fp32; the fp64 row of a runtime table keeps the whole chain's W_i (9 values per joint) live
+// across the obstacle loop and takes the registers it needs at one wave, like force_min_waves (profiles/link_contact.md).
+// No LDS: a row's K * 7 obstacle values are contiguous per lane.
+template <class A, class T>
+constexpr int link_contact_min_waves() {
+  return (A::kStatic || sizeof(T) < 8) ? 2 : kMinWaves;
+}
+template <class A, class T>
+__global__ void __launch_bounds__(kBlock, (link_contact_min_waves<A, T>()))
+link_contact_kernel(A arm, LinkContactP<T> P, long B, LinkContactIO<T> io) {
+  ABRK_ROW_INDEX
+  link_contact_body<A, T>(b, arm, P, io);
+}
+
 template <class A, class T>
 __global__ void __launch_bounds__(kBlock, kMinWaves)
 ik_kernel(A arm, IkP<T> P, long B, const T* __restrict__ qg, const T* __restrict__ tg, T* __restrict__ pp,
@@ -826,6 +843,11 @@ struct ForceArgs {
   const void *q, *dq, *target, *tv, *cmd, *force;  // tv may be null
   void *integ, *u;
 };
+struct LinkContactArgs {
+  const void* P;  // LinkContactP<T>
+  const void *q, *dq, *obstacle;
+  void *tau, *report;  // report may be null
+};
 struct LawArgs {
   const void* P;  // OscP<T>
   const void *J, *M, *g, *c, *xyz, *R, *q, *dq, *target, *tv, *une;
@@ -881,6 +903,7 @@ struct ArmOps {
   hipError_t (*plant_load)(int dtype, const LaunchArgs&, const PlantLoadArgs&);
   hipError_t (*contact)(int dtype, const LaunchArgs&, const ContactArgs&);
   hipError_t (*force)(int dtype, const LaunchArgs&, const ForceArgs&);
+  hipError_t (*link_contact)(int dtype, const LaunchArgs&, const LinkContactArgs&);
 };
 hipError_t launch_twolink_step(int dtype, const LaunchArgs& la, const void* K, void* q, void* dq, const void* u);
 
@@ -1024,6 +1047,12 @@ struct Launch {
                        *static_cast<const ForceP<T>*>(a.P), la.B, io);
     return hipGetLastError();
   }
+  static hipError_t link_contact(const LaunchArgs& la, const LinkContactArgs& a) {
+    const LinkContactIO<T> io{(const T*)a.q, (const T*)a.dq, (const T*)a.obstacle, (T*)a.tau, (T*)a.report};
+    hipLaunchKernelGGL((link_contact_kernel<A, T>), grid_for(la.B), dim3(kBlock), 0, la.stream, arm_of(la),
+                       *static_cast<const LinkContactP<T>*>(a.P), la.B, io);
+    return hipGetLastError();
+  }
   static hipError_t rollout(const LaunchArgs& la, const RolloutArgs& a) {
     if constexpr (A::N == 2) {
       with_rollout_variant(a.fast, a.use_C != 0, [&](auto uc, auto km) {
@@ -1089,7 +1118,8 @@ struct OpsFor {
                              &by_dtype<&LD::plant_fx, &LF::plant_fx>,
                              &by_dtype<&LD::plant_load, &LF::plant_load>,
                              &by_dtype<&LD::contact, &LF::contact>,
-                             &by_dtype<&LD::force, &LF::force>};
+                             &by_dtype<&LD::force, &LF::force>,
+                             &by_dtype<&LD::link_contact, &LF::link_contact>};
     return &o;
   }
 };

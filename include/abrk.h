@@ -530,6 +530,54 @@ int abrk_force_control_batch(int arm_id, int dtype, const abrk_force_params* par
                              const void* cmd, const void* force, void* integ, void* u, int device, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Whole-arm contact: the arm's link segments as capsules against per-row sphere obstacles.  One kernel per tick, in the
+ * shape of abrk_contact_step_batch, that WRITES the plant's joint-space disturbance: record { law;
+ * abrk_link_contact_step_batch -> tau; abrk_plant_step_fx_batch(tau_ext = tau) } and an elbow that passes through a
+ * sphere is pushed out of it inside a replayed plan.  The spheres are those of AvoidObstacles
+ * (abrk_avoid_obstacles_generate_batch), so a loop can show whether avoidance kept the arm clear.
+ *
+ * Segments.  Segment i (0 <= i < N) runs from a_i, the origin of joint_i, to b_i, the origin of joint_{i+1}; for the
+ * last segment b_i is the origin of EE.  These are the segments of avoid_obstacles.py:61-68.  Segment i is a body of
+ * link i+1: joints 0..i move it.  It has a radius r_i = link_radius[i], the same for every row; r_i < 0 switches the
+ * segment off.  A segment with |b-a|^2 == 0 is skipped.
+ * Obstacles.  Row b has K spheres of its own (1 <= K <= ABRK_LINK_CONTACT_MAX_OBSTACLES), `obstacle` [B,K,7] of `dtype`
+ * = cx, cy, cz, R, k, c, mu; the spheres are at rest; the first four columns are the AvoidObstacles obstacle.
+ * Per pair, for every (obstacle, segment), obstacle-major and segment-minor:
+ *   t     = clamp((c - a).(b - a) / |b - a|^2, 0, 1)        x = a + t (b - a)   (x = b exactly at t = 1)
+ *   e     = x - c;  d = |e|;  delta = R + r_i - d            penetration; delta <= 0: nothing
+ *   n     = e / d                                            from the obstacle to the link; d == 0: n = 0 (counted, no force)
+ *   v     = Jx dq,  Jx = J("link{i+1}", q, x = the material point at x)[:3]     (columns j > i are zero)
+ *   vn    = n.v;  fn = max(0, k delta - c vn)                Kelvin-Voigt, no adhesion - the law of the contact section
+ *   vt    = v - vn n;  f = fn n - mu fn vt / sqrt(|vt|^2 + vs^2)
+ *   tau_c += Jx^T f                                          written to tau [B,n], or added to it (accumulate != 0)
+ * The force acts at the axis point x, as the tip force of abrk_contact_step_batch acts at the sphere's centre; the moment
+ * r_i n x f of the friction about the axis is NOT MODELLED, nor are planes against capsules, link against link, or a
+ * velocity of the obstacles.  tau entries of joints past the segment get exact zeros from that pair.  A row with no
+ * pushing pair gets tau_c = 0 exactly; with accumulate its tau is left untouched to the bit.  The force is that of the
+ * start of the tick: the stability note of the contact section, on k h^2 / m_eff, applies unchanged.
+ * `report` [B,8] (optional): F = the sum of f in the world frame [3]; the deepest delta over the active pairs (negative:
+ * clear of everything; the lowest finite value where no pair is active); the number of pairs with delta > 0; the segment index, the
+ * obstacle index and the t of the deepest pair (the first in loop order on a tie).
+ *
+ * Recordable into a plan like every entry point, host or device pointers.  `obstacle` is read with ordinary loads at
+ * every launch, so an obstacle moved between two replays takes effect.  A HOST obstacle array is validated before it is
+ * staged - anything non-finite, R <= 0, a negative k, c or mu: ABRK_EINVAL with the row and the obstacle in the message.
+ * A DEVICE array is NOT validated, as with the surfaces.  ABRK_EINVAL also for params: n_obstacles outside
+ * 1..ABRK_LINK_CONTACT_MAX_OBSTACLES, vs <= 0, a non-finite radius among the first N, every segment off.
+ * --------------------------------------------------------------------------------- */
+#define ABRK_LINK_CONTACT_MAX_OBSTACLES 8
+typedef struct abrk_link_contact_params {
+  int32_t n_obstacles;    /* 1..ABRK_LINK_CONTACT_MAX_OBSTACLES */
+  double link_radius[7];  /* the first N are used; < 0: that segment is off */
+  double vs;              /* > 0 */
+  int32_t accumulate;
+} abrk_link_contact_params;
+
+int abrk_link_contact_step_batch(int arm_id, int dtype, const abrk_link_contact_params* params, int64_t B, const void* q,
+                                 const void* dq, const void* obstacle, void* tau, void* report /* or NULL */, int device,
+                                 void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Iterative inverse kinematics: InverseKinematics.generate_path
  * (abr_control/controllers/path_planners/inverse_kinematics.py:28-135) for B independent paths, all
  * n_timesteps iterations of a path inside one kernel (each iteration: Tx, J, quaternion of the EE, two

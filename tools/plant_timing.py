@@ -37,6 +37,15 @@ and the report on; and, at 4096 rows, the recorded tick { force law; contact; pl
 { plant_step } per replayed tick.  The protocol of --contact: same rounds, ratios to the plain step of the same rounds.
 
     python tools/plant_timing.py --force [--rows-fx 1048576]
+
+--links: the whole-arm contact step beside what it replaces, in the same run (profiles/link_contact.md): UR5 and Jaco2,
+fp64 and fp32, at 4096 and 1 M rows - Obstacles.apply with K = 1, 4 and 8 spheres per row and the report on, every link
+segment a capsule of 40 mm, the spheres placed at the middle of the row's own segments so that about two rows in three
+touch (the share is in the output); (a) contact.contact_step with four surfaces; (b) N contact_step calls, one per link
+frame, the later ones with accumulate - covering the links with points, as include/abrk.h advised before.  The protocol
+of --contact: same rounds; ratio_to_contact_s4 and ratio_to_n_calls are to those two of the same rounds.
+
+    python tools/plant_timing.py --links [--rows-fx 1048576]
 """
 import argparse
 import json
@@ -215,6 +224,96 @@ def contact_leg(rows_large):
     print(json.dumps(res))
 
 
+def links_leg(rows_large):
+    import abr_control_amd as a
+    from abr_control_amd import _abi, contact
+    from abr_control_amd.arms import jaco2, ur5
+
+    s = a.Stream(0)
+    rounds = 5
+    res = {"leg": "links", "device": a.device_name(0), "warmup": WARMUP, "timed": TIMED, "rounds": rounds, "us": {}}
+    e0, e1 = a.Event(0), a.Event(0)
+
+    def one_round(fn):
+        for _ in range(WARMUP):
+            fn()
+        s.sync()
+        ts = []
+        for _ in range(TIMED):
+            e0.record(s)
+            fn()
+            e1.record(s)
+            s.sync()
+            ts.append(e1.elapsed_ms_since(e0) * 1e3)
+        return ts
+
+    for name, make in (("ur5", ur5.Config), ("jaco2", jaco2.Config)):
+        res["us"][name] = {}
+        for dtype in (np.float64, np.float32):
+            rc = make(dtype=dtype)
+            n = rc.N_JOINTS
+            res["us"][name][np.dtype(dtype).name] = {}
+            for B in (4096, rows_large):
+                rng = np.random.RandomState(0)
+                q0, dq0 = rng.uniform(-1.9, 1.9, (B, n)).astype(dtype), rng.uniform(-2, 2, (B, n)).astype(dtype)
+                q, dq = a.DeviceArray.from_numpy(q0), a.DeviceArray.from_numpy(dq0)
+                ends = [np.asarray(rc.Tx(f"joint{i}", q0), dtype=np.float64) for i in range(n)]
+                ends.append(np.asarray(rc.Tx("EE", q0), dtype=np.float64))
+
+                def plane_table(frame, S, point):
+                    # planes through each row's own point, as in the --contact leg: delta = +-25 mm
+                    nrm = rng.normal(size=(B, S, 3))
+                    nrm /= np.linalg.norm(nrm, axis=2, keepdims=True)
+                    delta = np.where(np.arange(B) % 3 == 1, -0.025, 0.025)[:, None] * np.ones((1, S))
+                    planes = np.zeros((B, S, 8))
+                    planes[:, :, :3] = nrm
+                    planes[:, :, 3] = np.einsum("bsi,bi->bs", nrm, point) + delta
+                    planes[:, :, 4:] = [2e4, 100.0, 0.5, 0.0]
+                    return a.ContactSurfaces(rc, B, planes.astype(dtype).astype(np.float64), frame=frame, stream=s)
+
+                s4 = plane_table("EE", 4, ends[n])
+                per_link = [plane_table(f"link{i + 1}", 1, np.asarray(rc.Tx(f"link{i + 1}", q0), dtype=np.float64))
+                            for i in range(n)]
+                worlds = {}
+                for K in (1, 4, 8):
+                    # sphere o of a row at the middle of segment (o + row) % n, its centre R + r -+ 25 mm from the axis
+                    obs = np.zeros((B, K, 7))
+                    for o in range(K):
+                        seg = (o + np.arange(B)) % n
+                        mid = np.stack([0.5 * (ends[i] + ends[i + 1]) for i in range(n)])[seg, np.arange(B)]
+                        d = rng.normal(size=(B, 3))
+                        d /= np.linalg.norm(d, axis=1, keepdims=True)
+                        delta = np.where(np.arange(B) % 3 == 1, -0.025, 0.025)
+                        obs[:, o, :3] = mid + d * (0.05 + 0.04 - delta)[:, None]
+                        obs[:, o, 3:] = [0.05, 2e4, 100.0, 0.5]
+                    worlds[K] = a.Obstacles(rc, B, obs.astype(dtype).astype(np.float64), link_radius=0.04, stream=s)
+
+                def n_calls():
+                    tau = per_link[0].apply(q, dq)
+                    for t in per_link[1:]:
+                        t.apply(q, dq, tau=tau, accumulate=True)
+
+                forms = {"contact_s4": lambda: s4.apply(q, dq), "contact_n_calls": n_calls}
+                for K in worlds:
+                    forms[f"links_k{K}"] = (lambda w: lambda: w.apply(q, dq))(worlds[K])
+                ts = {k: [] for k in forms}
+                for _ in range(rounds):
+                    for k, fn in forms.items():
+                        ts[k] += one_round(fn)
+                out = {k: {"median_us": float(np.median(v)), "min_us": float(np.min(v)), "max_us": float(np.max(v))}
+                       for k, v in ts.items()}
+                esz = np.dtype(dtype).itemsize
+                for K in worlds:
+                    o = out[f"links_k{K}"]
+                    o["ratio_to_contact_s4"] = o["median_us"] / out["contact_s4"]["median_us"]
+                    o["ratio_to_n_calls"] = o["median_us"] / out["contact_n_calls"]["median_us"]
+                    o["bytes_per_row"] = (3 * n + 7 * K + 8) * esz
+                    o["gbytes_per_s"] = o["bytes_per_row"] * B / o["median_us"] * 1e-3
+                    o["rows_touching"] = float((worlds[K].report()["n_contacts"] > 0).mean())
+                res["us"][name][np.dtype(dtype).name][str(B)] = out
+    print(json.dumps(res))
+
+
 def force_leg(rows_large):
     import abr_control_amd as a
     from abr_control_amd import _abi, engine
@@ -318,12 +417,15 @@ def main():
     ap.add_argument("--payload", action="store_true", help="time the payload step against the effects and the plain step")
     ap.add_argument("--contact", action="store_true", help="time the contact kernel against the plain step")
     ap.add_argument("--force", action="store_true", help="time the force-control law against the contact and plain steps")
+    ap.add_argument("--links", action="store_true", help="time the whole-arm contact against the contact step and N of them")
     ap.add_argument("--rows-fx", type=int, default=1 << 20)
     args = ap.parse_args()
     if args.force:
         return force_leg(args.rows_fx)
     if args.contact:
         return contact_leg(args.rows_fx)
+    if args.links:
+        return links_leg(args.rows_fx)
     if args.effects or args.payload:
         return effects_leg(args.rows_fx, payload=args.payload)
     import abr_control_amd as a
